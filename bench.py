@@ -12,9 +12,13 @@ pipeline.py): exact mutual feature NN -> RANSAC (RANSAC.py parameters) -> ICP
 Multi-GPU: one process per GPU -- under torchrun, or started by this script
 itself when --gpus N > 1 is given without a launcher -- barrier + synchronize
 around the timed loop, max over ranks; value = all pairs of the job / that time.
-Beside it: the PCIe-inclusive rate (host-resident inputs, `host_resident`), weak
-scaling at N > 1 (P pairs on every rank), the pair-parallel CPU baseline and the
-C2 / a4 / a10 / f1 / f2 / f4 / C5 side measurements at N = 1.
+A plain run does only that: set up, warm up, time the K steps, write the last
+timed step's records with --dump-outputs DIR, print the line.
+--full adds what takes runs of its own: the per-kernel split and rooflines, the
+stage split, the accuracy figures, the PCIe-inclusive rate (host-resident
+inputs, `host_resident`), weak scaling at N > 1 (P pairs on every rank), the
+pair-parallel CPU baseline and the C2 / a4 / a10 / f1 / f2 / f4 / C5 side
+measurements at N = 1.
 """
 from __future__ import annotations
 
@@ -48,12 +52,19 @@ def parse():
     ap.add_argument("--points", type=int, default=8192)
     ap.add_argument("--dim", type=int, default=32)
     ap.add_argument("--feat-noise", type=float, default=1.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the per-kernel split and rooflines, the stage "
+                         "split, the accuracy figures, the host-resident legs, weak scaling (N > 1), "
+                         "the CPU baseline and the side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records the last timed step returned as DIR/records.npy (f64)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-host-resident", action="store_true",
-                    help="skip the PCIe-inclusive (host-resident inputs) measurement")
+                    help="with --full: skip the PCIe-inclusive (host-resident inputs) measurement")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the C2 / a4 / a10 / f1 / f4 side measurements")
+                    help="with --full: skip the C2 / a4 / a10 / f1 / f4 side measurements")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as one captured HIP graph (measured: no gain at 256 pairs, "
                          "slower at 32 / 64 where the cooperative launches are recorded)")
@@ -64,7 +75,10 @@ def parse():
     ap.add_argument("--streams", type=int, default=1,
                     help="split the rank's shard into this many sub-batches run concurrently on "
                          "their own HIP streams (1..4)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args):
@@ -1237,7 +1251,7 @@ def main():
     params = default_params(seed=0)
     pair_ids = np.arange(first, first + P, dtype=np.int32)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(batch, params, args.cpu_budget, pair_ids)  # before any GPU call
 
     rank, world, local = dist_setup()
@@ -1281,10 +1295,49 @@ def main():
     torch.cuda.synchronize()
     # the headline: K steps with nothing else in the stream
     wall, rec = run_timed(step, args.steps, 0, world)
-    # the per-kernel split from K more steps with libpcr's HIP events around the
-    # named kernels (the events add their own packets, so these steps are not
-    # the headline's)
+    recs = rec.cpu().numpy()   # the last timed step's records, before any other step
     graphed = pipe._graph is not None
+    total_pairs = args.pairs * args.steps   # every pair of the job, once per step
+    out = {
+        "metric": "TOF/PC pairs/sec (8192 pts)",
+        "value": total_pairs / wall,
+        "unit": "pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": wall / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32 xyz/features; f64 RANSAC/ICP; 1-term f16 MFMA screen (certified bound), "
+                 "f16x3-split MFMA screen for the rows it leaves, f64 exact re-rank",
+        "data": f"synthetic: procedural surface pairs, ROPNet-style augmentation, D={D} "
+                f"descriptors (noise {args.feat_noise}), generated per rank (seeds 1000+pair)",
+        "config": {"workload": "C4: batch of augmented TOF/PC pairs (featNN+RANSAC+ICP+Chamfer)",
+                   "pairs_total": args.pairs, "pairs_per_gpu": P, "points": N, "feature_dim": D,
+                   "streams_per_gpu": S,
+                   "ransac": "d=0.04 mutual n=3 edge0.9 dist0.04 (100000,0.999)",
+                   "icp": "d=0.02 (1e-6,1e-6,30)", "parallelism": f"pair-sharded x{world}",
+                   "inputs": "resident in HBM (--full: host_resident is the PCIe-inclusive rate)"},
+        "step_graph": graphed,  # the headline steps were replays of the captured step
+    }
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the gathered
+        # per-pair records (PairPipeline.records: T_ransac, T_icp, fitness / rmse
+        # of both, Chamfer, RANSAC iterations / status, mutual correspondences),
+        # one row per pair of the job in pair order (N > 1: one equal-size block
+        # per rank, a short shard's block zero-padded)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "records.npy"),
+                np.ascontiguousarray(recs, dtype=np.float64))
+    if not args.full:
+        if S > 1:
+            _lib.call("pcr_set_concurrency", 1)
+        finish(out, rank, world)
+        return
+    # --full from here.  The per-kernel split from K more steps with libpcr's HIP
+    # events around the named kernels (the events add their own packets, so these
+    # steps are not the headline's)
     pipe.use_graph = False
     _lib.profile_enable(True)
     for pid in range(_lib.PROF_SLOTS):
@@ -1335,7 +1388,6 @@ def main():
     stage_ms = per_launch_ms + per2_ms + extra_ms
     stage_tf = flops_launch / (stage_ms * 1e-3) / 1e12
 
-    recs = rec.cpu().numpy()
     mine = recs[rank * rows:rank * rows + P]
     T_icp = mine[:, 16:32].reshape(P, 4, 4)
     rre, rte = synth.rre_rte(T_icp[:, :3, :3], T_icp[:, :3, 3], batch.R, batch.t)
@@ -1355,28 +1407,7 @@ def main():
         al = (batch.src[p].astype(np.float64) @ T_icp[p, :3, :3].T + T_icp[p, :3, 3]).astype(np.float32)
         chamfer_samples += [(al, batch.tgt[p]), (batch.tgt[p], al)]
 
-    total_pairs = args.pairs * args.steps   # every pair of the job, once per step
-    out = {
-        "metric": "TOF/PC pairs/sec (8192 pts)",
-        "value": total_pairs / wall,
-        "unit": "pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": wall / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32 xyz/features; f64 RANSAC/ICP; 1-term f16 MFMA screen (certified bound), "
-                 "f16x3-split MFMA screen for the rows it leaves, f64 exact re-rank",
-        "data": f"synthetic: procedural surface pairs, ROPNet-style augmentation, D={D} "
-                f"descriptors (noise {args.feat_noise}), generated per rank (seeds 1000+pair)",
-        "config": {"workload": "C4: batch of augmented TOF/PC pairs (featNN+RANSAC+ICP+Chamfer)",
-                   "pairs_total": args.pairs, "pairs_per_gpu": P, "points": N, "feature_dim": D,
-                   "streams_per_gpu": S,
-                   "ransac": "d=0.04 mutual n=3 edge0.9 dist0.04 (100000,0.999)",
-                   "icp": "d=0.02 (1e-6,1e-6,30)", "parallelism": f"pair-sharded x{world}",
-                   "inputs": "resident in HBM (see host_resident for the PCIe-inclusive rate)"},
+    out.update({
         "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_F16_MFMA_TFLOPS,
                      "unit": "TFLOP/s", "frac": achieved / PEAK_F16_MFMA_TFLOPS,
                      "traffic": _pmc_traffic("featnn_row9<", "true>"),
@@ -1415,7 +1446,6 @@ def main():
         "roofline_icp": _sweep_roofline("a8 ICP", "icp_kernel", prof["icp"], icp_sweeps, N, cb_i, P),
         "kernels_ms_per_step": {k: v[0] / args.steps for k, v in prof.items()},
         "profiled_ms_per_step": pwall / args.steps * 1e3,  # the steps kernels_ms_per_step came from
-        "step_graph": graphed,  # the headline steps were replays of the captured step
         "featnn_rescan_rows_per_step": [r / args.steps for r in rescan_rows],
         "featnn_fallback_rows_per_step": [r / args.steps for r in fallback_rows],
         "stages_ms": stages,
@@ -1424,7 +1454,7 @@ def main():
                      "ransac_iters_mean": float(mine[:, 37].mean()),
                      "ransac_validations_mean": validated / P,
                      "mutual_corres_mean": float(mine[:, 39].mean())},
-    }
+    })
     if not args.no_host_resident:
         del pipe
         torch.cuda.empty_cache()
@@ -1480,6 +1510,12 @@ def main():
                             "f2_voxel": measure_voxel(wc),
                             "c3_flow": measure_c3(wc),
                             "c5_flow": measure_c5(wc)}
+    finish(out, rank, world)
+
+
+def finish(out, rank, world):
+    """Print rank 0's result line and release the process group and the library."""
+    from pointcloudregistration_amd import _lib
     if rank == 0:
         print(json.dumps(out))
     if os.environ.get("PCR_DUMP_MAPS"):

@@ -192,3 +192,32 @@ def test_graph_small_shard_equals_eager():
         pipe.run()
         torch.cuda.synchronize()
         assert _bits(pipe.records().cpu().numpy(), want)
+
+
+def test_bench_plain_run_dumps_the_timed_records(c4, tmp_path):
+    """A plain `bench.py` run prints the headline line alone and, with
+    --dump-outputs, writes the records its last timed step returned: for the
+    job's first 8 pairs (a pair's record does not depend on its batch) they are
+    the pipeline's records of the same workload bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
+                        "--warmup", "1", "--pairs", "8", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert np.isclose(line["value"], 8 / (line["ms_per_step"] * 1e-3), rtol=1e-9)
+    for key in ("roofline", "kernels_ms_per_step", "stages_ms", "accuracy", "host_resident",
+                "s8d_job", "cpu_baseline", "secondary"):
+        assert key not in line   # those legs run with --full only
+    assert sorted(os.listdir(out)) == ["records.npy"]
+    rec = np.load(out / "records.npy")
+    assert rec.dtype == np.float64
+    assert _bits(rec, c4["rec"][:8])

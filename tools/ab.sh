@@ -6,7 +6,7 @@
 #   LIBS="pointcloudregistration_amd/libpcr.so ab/libpcr_NAME.so" REPS=2 \
 #     bash tools/ab.sh featnn|bench|bench32|custom ["extra args"]
 # featnn : tools/featnn_bench.py (mutual path, 256 pairs) per-kernel ms
-# bench  : bench.py at 256 pairs (step ms + the kernel slots)
+# bench  : bench.py --full at 256 pairs (step ms + the kernel slots)
 # bench32: bench.py --pairs 32
 # custom : CMD="python3 ..." run with PCR_LIB set (output appended)
 # Every run has its own time limit; the script stops at the first failure.
@@ -26,7 +26,7 @@ for i in $(seq 1 "$REPS"); do
               python3 -c "import json,sys; d=json.load(open('$OUT/$tag.$i.json')); print('$tag', $i, json.dumps(d['ms']), d['rescan_rows'])" ;;
       bench|bench32)
               P=256; [ "$MODE" = bench32 ] && P=32
-              PCR_LIB=$L timeout -k 10 180 python3 bench.py --pairs $P --no-secondary --no-cpu-baseline --no-host-resident $EXTRA \
+              PCR_LIB=$L timeout -k 10 180 python3 bench.py --pairs $P --full --no-secondary --no-cpu-baseline --no-host-resident $EXTRA \
                 > "$OUT/$tag.$i.json" 2> "$OUT/$tag.$i.err" || exit 3
               python3 -c "import json; d=json.load(open('$OUT/$tag.$i.json')); print('$tag', $i, $P, round(d['ms_per_step'],3), {k: round(v,3) for k,v in d['kernels_ms_per_step'].items()})" ;;
       custom) PCR_LIB=$L timeout -k 10 300 $CMD >> "$OUT/$tag.log" 2>&1 || exit 3

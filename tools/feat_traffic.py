@@ -1,6 +1,6 @@
 """Per-step HBM bytes of the feature stage from a tools/pmc_traffic.sh summary
-(FETCH_SIZE already doubled for gfx950; bench.py --steps 2 --warmup 1 plus the
-profiled pass = `steps` steps).  usage: python tools/feat_traffic.py SUMMARY.json [steps]"""
+(FETCH_SIZE already doubled for gfx950; bench.py --full --steps 2 --warmup 1 plus
+the profiled pass = `steps` steps).  usage: python tools/feat_traffic.py SUMMARY.json [steps]"""
 import json
 import sys
 

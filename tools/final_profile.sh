@@ -17,10 +17,10 @@ rc=$?; echo "pytest rc $rc"; tail -2 $T/pytest_gpu.txt
 case $rc in 124|134|137|139) exit 11;; esac
 timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $T/smoke.txt 2>&1 || { tail -20 $T/smoke.txt; exit 12; }
 tail -2 $T/smoke.txt
-timeout -k 10 600 python bench.py > $T/bench.json 2> $T/bench.err || { tail -20 $T/bench.err; exit 13; }
+timeout -k 10 600 python bench.py --full > $T/bench.json 2> $T/bench.err || { tail -20 $T/bench.err; exit 13; }
 python3 -c "import json;d=json.loads(open('$T/bench.json').read().strip().splitlines()[-1]);print('value',round(d['value']),'ms',round(d['ms_per_step'],3))"
 for P in 32 64; do
-  timeout -k 10 300 python bench.py --pairs $P --no-secondary --no-cpu-baseline > $T/bench_${P}pairs.json 2> $T/bench_$P.err || { tail -5 $T/bench_$P.err; exit 14; }
+  timeout -k 10 300 python bench.py --pairs $P --full --no-secondary --no-cpu-baseline > $T/bench_${P}pairs.json 2> $T/bench_$P.err || { tail -5 $T/bench_$P.err; exit 14; }
   python3 -c "import json;d=json.loads(open('$T/bench_${P}pairs.json').read().strip().splitlines()[-1]);print($P,'pairs ms',round(d['ms_per_step'],3))"
 done
 fi

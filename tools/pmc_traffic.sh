@@ -14,7 +14,7 @@ OUT=${1:-gpurun_out/pmc_traffic}
 mkdir -p "$OUT"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d "$OUT/$c" -o run --output-format csv \
-    -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-host-resident > "$OUT/$c.log" 2>&1
+    -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-secondary --no-host-resident > "$OUT/$c.log" 2>&1
   rc=$?
   echo "pmc $c rc=$rc"
   [ $rc -eq 0 ] || exit $rc
