@@ -1098,19 +1098,44 @@ struct RowArgs5 {
 __device__ unsigned long long g_featnn_fallback_rows[2];
 
 // featnn_row9's column terms (after the packs and their repairs): the packs
-// stored f32(|x s|^2) per row, -1 on padding rows; here ct = f32(that + B) with
-// B the pair's smallest power of two above both clouds' max |x s|^2 (from the
-// packs' max norms, a rounding's margin added), so every screened value
-// ct_j - 2 x.y_j >= B - |x|^2 > 0 (unsigned order = float order) and ct lies in
-// [B, 2B] (2B - ct exact).  Padding rows: 16 B, above every real value (< 4 B).
-// A pair with a non-finite norm takes B = 2^60 (its rows certify nothing).
+// stored f32(|x s|^2) per row, -1 on padding rows; here ct = f32(that + B), B the
+// pair's bias.  The sweep, the regroup and the finish order the screened values
+//   v = fl(ct_j - 2 f16(x).f16(y_j))
+// by their bit patterns as unsigned integers, which is the float order only for
+// v >= 0, so B is sized against the screen's worst excursion, not against
+// max |x|^2.  With M the larger of the two clouds' max norms (fmax, gmax), E the
+// larger of their max split errors |x - f16(x)| (femax, gemax) and u = 2^-24:
+//   2 f16(x).f16(y) <= |f16(x)|^2 + |f16(y)|^2          (|f16(x) - f16(y)|^2 >= 0)
+//   |f16(x)|^2 <= (|x| + E)^2 <= M^2 + 2 M E + E^2
+//   |f16(y)|^2 <= |y|^2 + 2 M E + E^2
+//   ct_j >= |y_j|^2 + B - u (2 M^2 + B)(1 + 2^-20)       (f32 |y|^2, then + B)
+//   the MFMA chain (C = ct_j, 16 S <= 32 products): 2 (16 S + 2) u (|C| +
+//   sum |products|) <= 68 u (B + M^2 + 2 (M + E)^2)
+// so v >= B - Q - u (2 M^2 + B)(1 + 2^-20) - 68 u (B + 3 Q), Q = M^2 + 4 M E +
+// 2 E^2, which is > B (1 - 1.7e-5) - Q for Q < B: v > 0 whenever
+//   B >= Q (1 + 2^-15)                                    ((1 + 2^-15)(1 - 1.7e-5) > 1)
+// (f16 operands the MFMA flushes only shrink |f16(.)|; the f32 roundings of M and
+// E, 2^-23 relative, are inside the margin's rest, 1.4e-5).  B is the smallest power
+// of two above Q (1 + 2^-15) + 1.  Then also |y|^2 <= M^2 < B: ct lies in [B, 2B]
+// and 2B - ct is exact; and v <= 2B + 2 (M + E)^2 < 4B: the padding rows' 16 B is
+// above every real value.  row_tail / one_term_fails read B from cbias, so their
+// u B terms follow it.
+// Non-finite: the packs max the norms' bit patterns, so a cloud with a NaN row
+// has the NaN pattern as its max and fmaxf against the other cloud's would drop
+// it.  Each cloud's max is tested on its own: if either is not finite (or past
+// the split's range) the pair takes B = 2^60, under which its rows certify
+// nothing (u B is above every gap) and every finite value is ~2^60 > 0.
 __global__ __launch_bounds__(256) void feat_colterms(float *fct, float *gct, int ntn, int ntm,
-                                                     const unsigned *fmax, const unsigned *gmax, float *cbias) {
+                                                     const unsigned *fmax, const unsigned *gmax,
+                                                     const unsigned *femax, const unsigned *gemax, float *cbias) {
     const int p = blockIdx.y, role = blockIdx.z;
-    const float mf = __builtin_fmaxf(__uint_as_float(fmax[p]), __uint_as_float(gmax[p]));
+    const float mx = __uint_as_float(fmax[p]), my = __uint_as_float(gmax[p]);
+    const float ex = __uint_as_float(femax[p]), ey = __uint_as_float(gemax[p]);
     double B = 0x1p60;
-    if (mf < 0x1p50f) {
-        const double m2 = (double)mf * (double)mf * (1.0 + 0x1p-18) + 1.0;
+    // (each comparison is false for a NaN)
+    if (mx < 0x1p50f && my < 0x1p50f && ex < 0x1p50f && ey < 0x1p50f) {
+        const double M = (double)__builtin_fmaxf(mx, my), E = (double)__builtin_fmaxf(ex, ey);
+        const double m2 = (M * M + 4.0 * M * E + 2.0 * E * E) * (1.0 + 0x1p-15) + 1.0;
         const int e = (int)((__double_as_longlong(m2) >> 52) & 0x7ff) - 1023;  // m2 in [2^e, 2^(e+1))
         B = __builtin_ldexp(1.0, e + 1);
     }
@@ -2612,7 +2637,7 @@ static int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax,
         PCR_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(feat_colterms, dim3(cdiv(std::max(ntn, ntm) * 32, 256), P, 2), dim3(256), 0, s, v.fct, v.gct,
-                       ntn, ntm, v.fmax, v.gmax, v.cbias);
+                       ntn, ntm, v.fmax, v.gmax, v.femax, v.gemax, v.cbias);
     PCR_LAUNCH_CHECK();
     prof_end(s, kProfFeatPack);
     return PCR_OK;

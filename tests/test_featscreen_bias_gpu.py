@@ -1,0 +1,101 @@
+"""GPU: the 1-term feature screen's bias B (feat_colterms, csrc/featnn.hip) at the
+inputs where the unsigned order of its values can break.
+
+featnn_row9's values are ct_j - 2 f16(x).f16(y_j), ct_j = f32(|y_j|^2 + B), and
+the sweep, the regroup and the finish take minima of their BIT PATTERNS as
+unsigned integers: a value below zero sorts above +inf and its column is lost
+with no fallback.  Two inputs reach below B - |x|^2:
+  A. boundary rows (featscreen_cases.boundary_pair): |x s|^2 just below a power
+     of two with f16(x s) rounded up, and an exact twin in the other cloud -- the
+     twin's value is B - |x s|^2 - 2 (|f16(x s)|^2 - |x s|^2);
+  B. a NaN / inf in one cloud only (featscreen_cases.onesided_pair), whose finite
+     rows are ~8x the other cloud's: a bias sized from the finite cloud alone is
+     below those rows' |x s|^2.
+test_featscreen_model_cpu.py shows on the CPU that the cases are adversarial.
+
+Bar: bit-exact -- nn12, n_corres and the correspondence prefix equal the
+oracle's (exact f64), on the shipped path (featnn_row9), on the featnn_row8
+1-term passes (PCR_FEAT_ROW9=0: a fixed 2^21 bias) and on the 3-term screens
+alone (PCR_FEAT_ONE=0); a failure of the first alone is the row9 bias."""
+import numpy as np
+import pytest
+
+import featscreen_cases as fc
+from pointcloudregistration_amd import registration as reg
+
+pytestmark = pytest.mark.gpu
+
+PATHS = {"row9": {}, "row8": {"PCR_FEAT_ROW9": "0"}, "three_term": {"PCR_FEAT_ONE": "0"}}
+_ORACLE = {}
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _expected(oracle, key, F, G):
+    """the oracle's nn12 / nn21 per pair, computed once per case"""
+    if key not in _ORACLE:
+        _ORACLE[key] = [(oracle.featnn(F[p], G[p]), oracle.featnn(G[p], F[p])) for p in range(len(F))]
+    return _ORACLE[key]
+
+
+def _check(oracle, monkeypatch, key, F, G, mutual, path):
+    exp = _expected(oracle, key, F, G)
+    for k, v in PATHS[path].items():
+        monkeypatch.setenv(k, v)
+    co, nc, nn12 = reg.feature_correspondences(F, G, mutual_filter=mutual)
+    co, nc, nn12 = _np(co), _np(nc), _np(nn12)
+    if path == "row9":
+        a12, a21 = reg.feature_match(F, G)
+        co2, nc2 = reg.correspondences(a12, a21, mutual_filter=mutual)
+        co2, nc2 = _np(co2), _np(nc2)
+    for p, (e12, e21) in enumerate(exp):
+        want = oracle.corres(e12, e21, mutual, 3)
+        bad = np.flatnonzero(nn12[p] != e12)
+        assert bad.size == 0, (p, bad[:8], nn12[p][bad[:8]], e12[bad[:8]])
+        assert int(nc[p]) == len(want), (p, int(nc[p]), len(want))
+        assert np.array_equal(co[p, :len(want)], want), p
+        if path == "row9":  # == the two-call path
+            assert int(nc2[p]) == len(want) and np.array_equal(co2[p, :len(want)], want), p
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("mutual", [True, False])
+@pytest.mark.parametrize("name", list(fc.BIAS_CASES))
+def test_boundary_rows_vs_oracle(oracle, monkeypatch, name, mutual, path):
+    """d{D}_{where}_{side}_t{t}: D = 32 (register pack), 16, 24 (LDS pack; 16
+    non-zero elements per boundary row); `sample`: the boundary rows are inside
+    the first 64 rows and set feat_sample's speculative scale (|a s| < 2^11,
+    f16 spacing 1); `tail`: they come only after row 64 behind filler 64x
+    smaller, so the pair is flagged and takes the repair pack and the full-max
+    scale (|a s| < 2^12, f16 spacing 2); `f` / `g`: the boundary rows in F with
+    their twins in G, or the reverse (pass 1 meets them as rows or as columns)."""
+    c = fc.BIAS_CASES[name]
+    _check(oracle, monkeypatch, name, c["F"][None], c["G"][None], mutual, path)
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("mutual", [True, False])
+def test_boundary_batch_per_pair_bias(oracle, monkeypatch, mutual, path):
+    """P = 5, one B per pair: boundary pairs at x 2^-9 (sample scale) and x 2^7
+    (repair scale), two ordinary random pairs, a pair with boundary rows in G
+    only (gmax alone carries the maximum)."""
+    _, F, G = fc.bias_batch()
+    _check(oracle, monkeypatch, "batch", F, G, mutual, path)
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("mutual", [True, False])
+@pytest.mark.parametrize("name", list(fc.ONESIDED_CASES))
+def test_onesided_nonfinite_vs_oracle(oracle, monkeypatch, name, mutual, path):
+    """{nan,inf}_{f,g}_{tail,sample}[_twins]: one row of F (pass 1's rows) or of G
+    (pass 2's rows) has a NaN / inf element, after row 64 or inside the sample
+    (either way the pack flags the pair: the repair scale, from the finite
+    maximum for a NaN, 1 for an inf).  The packs max the norms' bit patterns, so
+    that cloud's max norm is the NaN pattern (fmaxf against the other cloud's
+    returns the finite operand) or +inf (fmaxf keeps it: the non-finite branch,
+    B = 2^60).  `_twins`: the finite cloud also holds full-scale copies, the
+    max-norm row among them, so its max norm equals the big cloud's."""
+    c = fc.ONESIDED_CASES[name]
+    _check(oracle, monkeypatch, name, c["F"][None], c["G"][None], mutual, path)
