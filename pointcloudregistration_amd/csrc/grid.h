@@ -9,10 +9,18 @@
 // brute force.  Consumers that own a pair (RANSAC, ICP) copy the grid into LDS
 // as one float4 per point (x, y, z, index bits) and u16 slot starts (GridP4,
 // 16 B per point + 2 B per slot: 144 KiB at 8192 points).
+//
+// Dense r-cell layout (GridDense, round 7): where a cloud's bounding box is
+// small enough, RANSAC's sweeps use cells 1.005 r wide addressed without a
+// hash -- an occupancy bitmap with per-word ranks and one u16 point offset per
+// occupied cell, in the LDS area the slot table would take.  A query then
+// examines about half the candidates (no collisions, cells an eighth the
+// volume).  The build kernel chooses per pair (build_grids_auto); ICP, FPFH,
+// nnd and the default pcr_radius_nn keep the hashed grid.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "geom.h"
-
+#include "grid_dense.h"
 
 namespace pcr {
 
@@ -138,7 +146,7 @@ __device__ __forceinline__ void axis_gaps(double p, int c0, int c1, double cell,
 template <typename View, bool kSlot = false, int kW = 2, bool kClear = false>
 __device__ __forceinline__ int grid_query_exact(const View &g, double r, double thr, double px,
                                                 double py, double pz, double &d2out, int *slot = nullptr,
-                                                double *s12out = nullptr) {
+                                                double *s12out = nullptr, int *ncand = nullptr) {
     const QueryBox bx = query_box(px, py, pz, 1.001 * r * g.inv_cell, g.inv_cell);
     const int x0 = bx.x0, x1 = bx.x1, y0 = bx.y0, y1 = bx.y1, z0 = bx.z0, z1 = bx.z1;
     const double lim = thr * (1.0 + 1e-9);
@@ -220,6 +228,7 @@ __device__ __forceinline__ int grid_query_exact(const View &g, double r, double 
             const double b = __builtin_fmin(__builtin_fmin(face(px, x0, x1), face(py, y0, y1)), face(pz, z0, z1));
             rho2 = __builtin_fmin(b * b * (1.0 - 1e-12), (double)skip_min * (1.0 - 0x1p-20));
         }
+        if (ncand) *ncand = total;  // PCR_RANSAC_STATS: candidates this query examines
         int s = (int)(q[0] & 0xffffu), e = (int)(q[0] >> 16);
         // up to two candidates per step, both from the current range (one site
         // shifts the queue: a wave pays the shift once per step, not twice)
@@ -308,10 +317,87 @@ __device__ __forceinline__ int grid_query_exact(const View &g, double r, double 
 
 template <typename View, bool kSlot = false, int kW = 2>
 __device__ __forceinline__ int grid_query(const View &g, double r, double thr, double px,
-                                          double py, double pz, double &d2out, int *slot = nullptr) {
+                                          double py, double pz, double &d2out, int *slot = nullptr,
+                                          int *ncand = nullptr) {
     // (an f32-screened walk with a rigorous bound -- f64 only for the winner --
     // measured no faster in round 4: the LDS candidate gathers bind as much)
-    return grid_query_exact<View, kSlot, kW>(g, r, thr, px, py, pz, d2out, slot);
+    return grid_query_exact<View, kSlot, kW>(g, r, thr, px, py, pz, d2out, slot, nullptr, ncand);
+}
+
+// Dense r-cell grid of one cloud (HBM or LDS; grid_dense.h has the layout and
+// the index arithmetic).  No hash, so no collisions: a query examines only the
+// points of the cells its ball can reach.
+struct GridDense {
+    const float4 *pts;
+    DenseTab t;
+};
+
+// grid_query on the dense layout: same result, bit for bit (the nearest target
+// with d2 < thr, lowest index on ties, is a property of the point set; the
+// candidates only have to contain every point with d2 < thr, and d2 is the same
+// dist2 of the same f32 coordinates).  Each of the <= 3 x 3 (y, z) rows of the
+// box [p - 1.001 r, p + 1.001 r] that lies inside the grid and within reach
+// gives one contiguous candidate range (dense_ranges): its x-cells are trimmed
+// by the gap test, the <= 2 bitmap words over them give lo = rank + popcount
+// below and n = popcount inside, and the range is start[lo] .. start[lo + n].
+// The non-empty ranges are queued and walked flat, kW at a time from the current
+// range, as in grid_query_exact.  A query outside the grid costs the row tests only.
+template <int kW>
+__device__ __forceinline__ int grid_query_dense(const GridDense &g, double r, double thr, double px,
+                                                double py, double pz, double &d2out, int *ncand = nullptr) {
+    unsigned q[9];
+    int nq = 0, total = 0;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) q[c] = 0u;
+    dense_ranges(g.t, r, thr, px, py, pz, [&](int s0, int e0) {
+        if (e0 > s0) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+                if (k == nq) q[k] = (unsigned)s0 | ((unsigned)e0 << 16);
+            ++nq;
+            total += e0 - s0;
+        }
+    });
+    if (ncand) *ncand = total;
+    double best = __builtin_inf();
+    int bj = -1;
+    int s = (int)(q[0] & 0xffffu), e = (int)(q[0] >> 16);
+    while (total > 0) {
+        int sl[kW];
+        bool ok[kW];
+#pragma unroll
+        for (int u = 0; u < kW; ++u) {
+            ok[u] = u == 0 || s + u < e;
+            sl[u] = ok[u] ? s + u : s;
+        }
+        int took = 1;
+#pragma unroll
+        for (int u = 1; u < kW; ++u) took += ok[u] ? 1 : 0;
+        s += took;
+        total -= took;
+        if (s >= e) {  // next range: shift the queue down by one
+#pragma unroll
+            for (int k = 0; k < 8; ++k) q[k] = q[k + 1];
+            q[8] = 0u;
+            s = (int)(q[0] & 0xffffu);
+            e = (int)(q[0] >> 16);
+        }
+        float4 cv[kW];
+#pragma unroll
+        for (int u = 0; u < kW; ++u) cv[u] = g.pts[sl[u]];
+        double dd[kW];
+#pragma unroll
+        for (int u = 0; u < kW; ++u) dd[u] = dist2(px, py, pz, (double)cv[u].x, (double)cv[u].y, (double)cv[u].z);
+#pragma unroll
+        for (int u = 0; u < kW; ++u) {
+            if (ok[u] && dd[u] < thr) {
+                const int j = __float_as_int(cv[u].w);
+                if (dd[u] < best || (dd[u] == best && j < bj)) { best = dd[u]; bj = j; }
+            }
+        }
+    }
+    d2out = best;
+    return bj;
 }
 
 // Grids for P target clouds (device, workspace-backed; see grid.hip).
@@ -321,10 +407,36 @@ struct GridBatch {
     int S;
     int mstride;
     double cell;
+    // dense r-cell layout, chosen per pair by the build kernel (null / 0: none
+    // built, every pair hashed).  Pair p's tables lie at tab + p * tab_bytes:
+    // bits[words] u32, rank[words] u16, start[occ + 1] u16; hdr[p].mode says
+    // whether they are valid.  A hashed pair's grid is in pts / start as ever.
+    const GridHdr *hdr;
+    const char *tab;
+    int tab_bytes;
+    double dcell;
     __device__ GridView view(int p) const {
         return GridView{pts + (size_t)p * mstride, start + (size_t)p * (S + 1), S, cell, 1.0 / cell};
     }
+    __device__ bool dense(int p) const { return hdr != nullptr && hdr[p].mode == 1; }
+    // pair p's dense grid with the points at `lp` and the tables at `lt`
+    __device__ GridDense dense_at(int p, const float4 *lp, const char *lt) const {
+        const GridHdr h = hdr[p];
+        const uint32_t *b = (const uint32_t *)lt;
+        const uint16_t *rk = (const uint16_t *)(b + h.words);
+        return GridDense{lp, DenseTab{b, rk, rk + h.words, h.ox, h.oy, h.oz, h.DX, h.DY, h.DZ, 1.0 / dcell, (float)dcell}};
+    }
+    __device__ GridDense dense_view(int p) const {  // in HBM
+        return dense_at(p, pts + (size_t)p * mstride, tab + (size_t)p * tab_bytes);
+    }
 };
+
+// slots of the hashed grid: the power of two >= Mmax (>= 256), times slot_num / 2
+inline int grid_slots(int Mmax, int slot_num) {
+    int S = 256;
+    while (S < Mmax) S <<= 1;
+    return S / 2 * slot_num;
+}
 
 // bytes of the float4 LDS copy of one pair's grid (0 if it does not fit)
 inline size_t grid_lds4_bytes(int mstride, int S, size_t budget) {
@@ -353,6 +465,26 @@ __device__ inline GridP4 grid_lds4_view(const GridBatch &gb, char *lds) {
     return GridP4{lp, (const uint16_t *)(lp + gb.mstride), gb.S, gb.cell, 1.0 / gb.cell};
 }
 
+// dense twin of grid_to_lds4: pair p's sorted points, then its tables (bits,
+// rank, start: dense_table_bytes of them, in 4-byte words) behind them
+__device__ inline void grid_dense_to_lds(const GridBatch &gb, int p, int m, char *lds) {
+    const size_t o = (size_t)p * gb.mstride;
+    float4 *lp = (float4 *)lds;
+    for (int i = threadIdx.x; i < m; i += blockDim.x) lp[i] = gb.pts[o + i];
+    const GridHdr h = gb.hdr[p];
+    const int nw = (int)((dense_table_bytes(h.words, h.occ) + 3) >> 2);  // <= tab_bytes / 4 (the fit rule)
+    const uint32_t *src = (const uint32_t *)(gb.tab + (size_t)p * gb.tab_bytes);
+    uint32_t *dst = (uint32_t *)(lp + gb.mstride);
+    for (int i = threadIdx.x; i < nw; i += blockDim.x) dst[i] = src[i];
+    __syncthreads();
+}
+
+// view of a dense copy that grid_dense_to_lds placed at `lds`
+__device__ inline GridDense grid_dense_lds_view(const GridBatch &gb, int p, char *lds) {
+    const float4 *lp = (const float4 *)lds;
+    return gb.dense_at(p, lp, (const char *)(lp + gb.mstride));
+}
+
 // host: spatial (Morton-of-cell) order of each cloud's points, (P, Nmax) i32 in a
 // workspace slot; with perm, also the points themselves in that order, (P, Nmax, 3)
 // f32 in slot perm_slot (a sweep in spatial order then reads its 64-point chunk
@@ -365,5 +497,22 @@ int spatial_order(const float *pts, const int32_t *n, int P, int Nmax, double ce
 // slots -- fewer collisions -- where the consumer's LDS has room for them)
 int build_grids(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double r,
                 hipStream_t s, int ws_slot, GridBatch &out, double cell_factor = 2.01, int slot_num = 2);
+
+// host: like build_grids (slot_num as given), but one launch in which every
+// pair's workgroup chooses its layout: dense r-cell tables when
+// dense_table_bytes(words, occ) <= tab_bytes (and the cloud has at most
+// kDenseCellCap cells and kDenseMaxPoints points), else the hashed grid.  No
+// host synchronisation.  Needs grid_slots(Mmax, slot_num) <= 32768.
+int build_grids_auto(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double r, hipStream_t s,
+                     int ws_slot, GridBatch &out, int tab_bytes, int slot_num);
+
+// host: PCR_ERR_ARG unless every pair of an auto-built batch took the dense
+// layout (synchronises the stream: for the forced-dense test switches only)
+int require_all_dense(const GridBatch &g, int P, hipStream_t s, const char *who);
+
+// host: RANSAC's target grids (ransac.hip: the table area follows from its LDS
+// budget; PCR_RANSAC_GRID=hash|dense|auto)
+int build_ransac_grids(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double r, hipStream_t s,
+                       GridBatch &out);
 
 }  // namespace pcr

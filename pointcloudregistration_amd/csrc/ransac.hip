@@ -17,7 +17,10 @@
 //  * ransac_task_kernel: the round's tasks = the passing hypotheses below the
 //    pair's live bound, in iteration order;
 //  * ransac_sweep_kernel (persistent 1024-thread workgroups, one per CU, the
-//    task's target hash grid copied to LDS): validates the tasks of ALL pairs
+//    task's target grid copied to LDS -- the dense r-cell tables of grid.h
+//    where the pair's build chose them, else the hashed grid; the kernel reads
+//    the pair's header and branches, uniformly per workgroup): validates the
+//    tasks of ALL pairs
 //    speculatively and in parallel -- rank-major (every pair's first passing
 //    hypothesis, then every pair's second, ...) from a global counter, so a
 //    pair with many hypotheses no longer holds one CU for the whole launch
@@ -38,9 +41,16 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <type_traits>
 #include <vector>
 
 constexpr int kRansacKW = 4;  // candidates per grid-walk step in the sweeps (2 / 4 / 6 / 8 measured, round 4)
+// the same on the dense r-cell grid, whose ranges (one row of <= 3 cells of a
+// surface) hold two or three points: 2 / 4 and steps that run on into the next
+// range at 2 / 3 / 4 / 6 measured in round 7, all within 0.04 ms of each other and
+// 0.1 ms ahead of 4
+constexpr int kDenseKW = 2;
 
 namespace pcr {
 namespace {
@@ -89,6 +99,7 @@ struct RHeader {
     int active_count;  // pairs still active after the round
     int bad;           // replay met a task it needed that was never swept (bug guard)
     int n_done, n_cut, n_skip, n_chunks;  // diagnostics (PCR_RANSAC_STATS=1 prints them)
+    unsigned long long n_cand, n_query;   // candidates examined / grid queries made (one add per sweep)
 };
 
 static_assert(2 * sizeof(RHeader) / sizeof(int) <= 256, "ransac_hyp_kernel clears the headers with one thread per word");
@@ -247,6 +258,7 @@ struct Shared {  // LDS header (the grid copy follows)
     double Te[12];
     unsigned long long racc[kWaves];
     int rcnt[kWaves], rcin[kWaves];
+    unsigned rcand[kWaves], rqry[kWaves];  // diagnostics: candidates examined, queries made
     int chunk;     // next 64-query chunk of the running sweep
     int misses;    // source points without a correspondence so far in this sweep
     int task, lb, skip, gp;  // current task, its cut bound, skip flag, pair whose grid is loaded
@@ -302,6 +314,7 @@ __device__ TaskRes sweep_pair(const RArgs &a, Shared &sh, const Grid &gr, int p,
     const int nch = min((n + 63) >> 6, c_hi);
     unsigned long long acc = 0;
     int cnt = 0, cin = 0;
+    unsigned ncand = 0, nqry = 0;
     int lb = sh.lb;
     for (int nc = 1;; ++nc) {
         int c = 0;
@@ -309,6 +322,7 @@ __device__ TaskRes sweep_pair(const RArgs &a, Shared &sh, const Grid &gr, int p,
         c = __shfl(c, 0, 64);
         if (c >= nch) break;
         const int k = (c << 6) + lane;
+        nqry += (unsigned)min(64, n - (c << 6));  // wave-uniform
         int j = 0;
         if (k < n) {
             // the chunk's points: a contiguous run of the ordered copy, or gathered
@@ -321,7 +335,12 @@ __device__ TaskRes sweep_pair(const RArgs &a, Shared &sh, const Grid &gr, int p,
             }
             double px, py, pz, d2;
             xform12(Te, (double)sx, (double)sy, (double)sz, px, py, pz);
-            j = grid_query<Grid, false, kRansacKW>(gr, a.d, a.thr, px, py, pz, d2);
+            int nc1 = 0;
+            if constexpr (std::is_same_v<Grid, GridDense>)
+                j = grid_query_dense<kDenseKW>(gr, a.d, a.thr, px, py, pz, d2, &nc1);
+            else
+                j = grid_query<Grid, false, kRansacKW>(gr, a.d, a.thr, px, py, pz, d2, nullptr, &nc1);
+            ncand += (unsigned)nc1;
             if (j >= 0) { ++cnt; acc += (unsigned long long)(d2 * scale); }
             // written through (sc1): finish_task's release fence writes back the
             // XCD L2's dirty lines, and a sweep's targets are 32 KB of them
@@ -370,10 +389,17 @@ __device__ TaskRes sweep_pair(const RArgs &a, Shared &sh, const Grid &gr, int p,
         acc += __shfl_xor(acc, o, 64);
         cnt += __shfl_xor(cnt, o, 64);
         cin += __shfl_xor(cin, o, 64);
+        ncand += __shfl_xor(ncand, o, 64);
     }
-    if (lane == 0) { sh.racc[wid] = acc; sh.rcnt[wid] = cnt; sh.rcin[wid] = cin; }
+    if (lane == 0) { sh.racc[wid] = acc; sh.rcnt[wid] = cnt; sh.rcin[wid] = cin; sh.rcand[wid] = ncand; sh.rqry[wid] = nqry; }
     __syncthreads();
-    if (tid == 0) atomicAdd(&a.hdr->n_chunks, min(sh.chunk, max(nch - c_lo, 0)));
+    if (tid == 0) {
+        atomicAdd(&a.hdr->n_chunks, min(sh.chunk, max(nch - c_lo, 0)));
+        unsigned long long sc = 0, sq = 0;
+        for (int w = 0; w < kWaves; ++w) { sc += sh.rcand[w]; sq += sh.rqry[w]; }
+        atomicAdd(&a.hdr->n_cand, sc);
+        atomicAdd(&a.hdr->n_query, sq);
+    }
     TaskRes r{};
     for (int w = 0; w < kWaves; ++w) { r.acc += sh.racc[w]; r.cnt += sh.rcnt[w]; r.cin += sh.rcin[w]; }
     r.status = cut ? kCut : kDone;
@@ -561,8 +587,12 @@ __global__ __launch_bounds__(kThreads) void ransac_sweep_kernel(RArgs a) {
             continue;
         }
         char *glds = dsm + ((sizeof(Shared) + 15) & ~size_t(15));
+        // the pair's layout (dense r-cell tables or the hashed grid: the build
+        // kernel chose), uniform over the workgroup
+        const bool dense = kLds && a.grid.dense(p);
         if (kLds && sh.gp != p) {  // this pair's grid into LDS (kept while the next task is the same pair)
-            (void)grid_to_lds4(a.grid, p, cnt_of(a.n_tgt, p, a.Mmax), glds);
+            if (dense) grid_dense_to_lds(a.grid, p, cnt_of(a.n_tgt, p, a.Mmax), glds);
+            else (void)grid_to_lds4(a.grid, p, cnt_of(a.n_tgt, p, a.Mmax), glds);
             if (tid == 0) sh.gp = p;
         }
         double Te[12];
@@ -573,10 +603,14 @@ __global__ __launch_bounds__(kThreads) void ransac_sweep_kernel(RArgs a) {
         const int c_lo = h * nch / a.split, c_hi = (h + 1) * nch / a.split;
         int *gm = a.split > 1 ? &rs[r].misses : nullptr;
         TaskRes out;
-        if constexpr (kLds)
-            out = sweep_pair<kLds, RN>(a, sh, grid_lds4_view(a.grid, glds), p, n, K, Te, rs, r, cbuf, true,
-                                       c_lo, c_hi, gm, h, a.split);
-        else
+        if constexpr (kLds) {
+            if (dense)
+                out = sweep_pair<kLds, RN>(a, sh, grid_dense_lds_view(a.grid, p, glds), p, n, K, Te, rs, r, cbuf,
+                                           true, c_lo, c_hi, gm, h, a.split);
+            else
+                out = sweep_pair<kLds, RN>(a, sh, grid_lds4_view(a.grid, glds), p, n, K, Te, rs, r, cbuf, true,
+                                           c_lo, c_hi, gm, h, a.split);
+        } else
             out = sweep_pair<kLds, RN>(a, sh, a.grid.view(p), p, n, K, Te, rs, r, cbuf, true, c_lo, c_hi,
                                        gm, h, a.split);
         // every thread's target stores have completed before the result is published
@@ -648,8 +682,15 @@ __global__ __launch_bounds__(kThreads) void ransac_replay_kernel(RArgs a) {
         double Te[12];
         for (int k = 0; k < 12; ++k) Te[k] = s.bestT[k];
         if constexpr (kLds) {
-            const GridP4 gl = grid_to_lds4(a.grid, p, m, dsm + ((sizeof(Shared) + 15) & ~size_t(15)));
-            (void)sweep_pair<kLds, RN>(a, sh, gl, p, n, K, Te, nullptr, 0, bb, false);
+            char *glds = dsm + ((sizeof(Shared) + 15) & ~size_t(15));
+            if (a.grid.dense(p)) {
+                grid_dense_to_lds(a.grid, p, m, glds);
+                (void)sweep_pair<kLds, RN>(a, sh, grid_dense_lds_view(a.grid, p, glds), p, n, K, Te, nullptr, 0, bb,
+                                           false);
+            } else {
+                const GridP4 gl = grid_to_lds4(a.grid, p, m, glds);
+                (void)sweep_pair<kLds, RN>(a, sh, gl, p, n, K, Te, nullptr, 0, bb, false);
+            }
         } else {
             (void)sweep_pair<kLds, RN>(a, sh, a.grid.view(p), p, n, K, Te, nullptr, 0, bb, false);
         }
@@ -702,6 +743,32 @@ int env_int(const char *name, int dflt) {  // test hooks (PCR_RANSAC_WGS / _SLOT
 }
 
 }  // namespace
+
+// RANSAC's target grids.  PCR_RANSAC_GRID (test hook) = auto (default): the
+// build kernel gives every pair the dense r-cell tables when they fit the LDS
+// table area -- the 160 KB budget minus the Shared header minus 16 B per point
+// -- and the hashed 2.01 r grid otherwise; hash: the hashed grid for all;
+// dense: an error unless every pair is dense.  Clouds whose points do not fit
+// LDS at all keep the hashed grid in HBM.
+int build_ransac_grids(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double r, hipStream_t s,
+                       GridBatch &out) {
+    const char *e = getenv("PCR_RANSAC_GRID");
+    const bool want_hash = e && !strcmp(e, "hash"), want_dense = e && !strcmp(e, "dense");
+    PCR_REQUIRE(!e || !*e || want_hash || want_dense || !strcmp(e, "auto"), PCR_ERR_ARG,
+                "ransac: PCR_RANSAC_GRID=%s (hash, dense or auto)", e);
+    const size_t hdr = (sizeof(Shared) + 15) & ~size_t(15);
+    const size_t budget = 160 * 1024 - hdr;
+    const int S = grid_slots(Mmax, 3);
+    const bool can = !want_hash && Mmax <= kDenseMaxPoints && S <= 32768 && grid_lds4_bytes(Mmax, S, budget) > 0;
+    if (!can) {
+        PCR_REQUIRE(!want_dense, PCR_ERR_ARG, "ransac: PCR_RANSAC_GRID=dense, but %d points per cloud do not fit LDS", Mmax);
+        return build_grids(tgt, n_tgt, P, Mmax, r, s, 4, out, 2.01, 3);
+    }
+    const int tab = (int)((budget - (size_t)Mmax * 16) & ~size_t(15));
+    int rc = build_grids_auto(tgt, n_tgt, P, Mmax, r, s, 4, out, tab, 3);
+    if (rc != PCR_OK) return rc;
+    return want_dense ? require_all_dense(out, P, s, "ransac") : PCR_OK;
+}
 
 int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
                 const int32_t *n_src, const int32_t *n_tgt, const int32_t *corres,
@@ -766,7 +833,7 @@ int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
             a.order = Nmax > 0 ? order_in : nullptr;
             a.srcp = Nmax > 0 ? perm_in : nullptr;
         } else {
-            int rc = build_grids(tgt, n_tgt, P, Mmax, a.d, s, 4, a.grid, 2.01, 3);
+            int rc = build_ransac_grids(tgt, n_tgt, P, Mmax, a.d, s, a.grid);
             if (rc != PCR_OK) return rc;
             if (Nmax > 0) {
                 rc = spatial_order(src, n_src, P, Nmax, a.grid.cell, s, 13, &a.order, &a.srcp, 36);
@@ -779,7 +846,10 @@ int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
     const size_t budget = 160 * 1024 - hdr;
     const size_t gbytes = (a.d > 0.0 && Mmax > 0) ? grid_lds4_bytes(Mmax, a.grid.S, budget) : 0;
     const bool lds = gbytes > 0;
-    const size_t sm = lds ? hdr + gbytes : hdr;
+    // with dense tables in play the grid area is the points plus the whole table area
+    const size_t garea = a.grid.hdr ? std::max(gbytes, (size_t)Mmax * 16 + (size_t)a.grid.tab_bytes) : gbytes;
+    PCR_REQUIRE(!a.grid.hdr || (lds && garea <= budget), PCR_ERR_ARG, "ransac: dense grid tables without an LDS grid");
+    const size_t sm = lds ? hdr + garea : hdr;
     const void *hfn = nullptr, *sfn = nullptr, *rfn = nullptr;
     switch (a.rn) {
 #define PCR_RCASE(N)                  \
@@ -877,8 +947,16 @@ int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
             PCR_HIP_CHECK(hipStreamSynchronize(s));
             for (int r = 0; r < 2; ++r)
                 fprintf(stderr, "ransac gated round %d: tasks done %d cut %d skipped %d, chunks %d, active after %d, "
-                        "bad %d\n", r, h[r].n_done, h[r].n_cut, h[r].n_skip, h[r].n_chunks, h[r].active_count,
-                        h[r].bad);
+                        "bad %d, candidates %llu queries %llu (c_bar %.2f)\n", r, h[r].n_done, h[r].n_cut,
+                        h[r].n_skip, h[r].n_chunks, h[r].active_count, h[r].bad, h[r].n_cand, h[r].n_query,
+                        (double)h[r].n_cand / (double)std::max<unsigned long long>(1, h[r].n_query));
+            if (a.grid.hdr) {
+                std::vector<GridHdr> gh((size_t)P);
+                PCR_HIP_CHECK(hipMemcpy(gh.data(), a.grid.hdr, sizeof(GridHdr) * (size_t)P, hipMemcpyDeviceToHost));
+                int nd = 0;
+                for (int p = 0; p < P; ++p) nd += gh[p].mode == 1;
+                fprintf(stderr, "ransac grids: %d of %d pairs dense\n", nd, P);
+            }
         }
         return PCR_OK;
     }
@@ -906,9 +984,11 @@ int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
         PCR_HIP_CHECK(hipStreamSynchronize(s));
         PCR_REQUIRE(h.bad == 0, PCR_ERR_HIP, "ransac: %d pairs met an unswept task", h.bad);
         if (stats_env)
-            fprintf(stderr, "ransac round [%d,%d): tasks done %d cut %d skipped %d, chunks %d (%.2f full sweeps)\n",
+            fprintf(stderr, "ransac round [%d,%d): tasks done %d cut %d skipped %d, chunks %d (%.2f full sweeps), "
+                    "candidates %llu queries %llu (c_bar %.2f)\n",
                     a.b0, a.b1, h.n_done, h.n_cut, h.n_skip, h.n_chunks,
-                    h.n_chunks / (double)std::max(1, (Nmax + 63) / 64));
+                    h.n_chunks / (double)std::max(1, (Nmax + 63) / 64), h.n_cand, h.n_query,
+                    (double)h.n_cand / (double)std::max<unsigned long long>(1, h.n_query));
         if (a.b1 >= a.max_iter || h.active_count == 0) break;
         a.b0 = a.b1;
         a.b1 = std::min(a.max_iter, a.b0 + kRoundN);
