@@ -631,6 +631,60 @@ int32_t pcr_ndp_chamfer_max_points(void);
 int pcr_ndp_chamfer_prepare(const pcr_ndp_chamfer *c, const float *xs0, pcr_stream_t stream);
 int pcr_ndp_chamfer_step(const pcr_ndp_chamfer *c, pcr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Point-set sampling and grouping: fps, ball_query and sample_and_group of
+ * ROPNet/src/models/model_utils.py:6-102 (used by LocalFeatue.forward,
+ * TFMR.py:48-71) and c2p-net/ngenet/utils/process.py:57-115 (used by
+ * PPF.forward, ngenet/models/information_interactive.py:48-84).
+ *
+ * Shared contract.  Squared distance d2(a, b) = (dx*dx + dy*dy) + dz*dz in f32,
+ * every operation rounded (no FMA), the direct form; the reference's expanded
+ * |a|^2 + |b|^2 - 2 a.b agrees with it to rounding.  r2 is the f32 squared
+ * radius, (float)((double)radius * radius) for the reference's `radius ** 2`;
+ * j is a neighbour iff !(d2 > r2), so a distance equal to the radius is
+ * inside.  Ties go to the lowest index.  Non-finite coordinates give
+ * unspecified results.  All buffers are device memory; all three entries are
+ * asynchronous on `stream`; n >= 1 and n < 2^31 / 3.
+ *
+ * pcr_fps: farthest-point sampling.  xyz (b,n,3) f32, start (b) i32 with
+ *   0 <= start < n (a PRECONDITION the library cannot see: the values live on
+ *   the device; the kernel clamps them so that it never reads outside the
+ *   cloud), m >= 1, idx (b,m) i32.  Per cloud: dist[j] = 1e10f, cur = start;
+ *   for i < m: idx[i] = cur; for all j, d = d2(x[cur], x[j]) and dist[j] = d
+ *   where d < dist[j]; cur = the first index of max(dist).  m > n is legal
+ *   (the loop defines it).  One workgroup per cloud; clouds of up to 8192
+ *   points run from registers, larger ones keep the rest in the workspace,
+ *   with identical results.
+ *
+ * pcr_ball_query: xyz (b,n,3), query (b,q,3) f32, k >= 1, idx (b,q,k) i32,
+ *   count (b,q) i32 or NULL.  Row = the ascending indices j that are
+ *   neighbours of the query, cut to the first k; the columns after the last
+ *   one repeat the row's first neighbour; a row without neighbours holds n in
+ *   every column (the reference's sentinel).  count = the number of
+ *   neighbours before the cut (the reference's density is count / n).  k > n
+ *   is legal and pads the same way.
+ *
+ * pcr_group_ppf: sample_and_group with M = -1 (every point a centre) and the
+ *   point-pair features of LocalFeatue / PPF in one call.  xyz (b,n,3),
+ *   normals (b,n,3) f32 or NULL, r2 >= 0, k >= 1; idx (b,n,k) i32 or NULL
+ *   receives the ball query of xyz against itself.  C = 10 channels with
+ *   normals, 6 without; for centre i and its neighbour j, g = x_j - x_i:
+ *   0-2 x_i, 3-5 g, 6 angle(n_i, g), 7 angle(n_j, g), 8 angle(n_i, n_j),
+ *   9 |g|, with angle(a, c) = atan2f(|a x c|, a . c), cross components
+ *   a1*c2 - a2*c1 ..., norms sqrtf((v0*v0 + v1*v1) + v2*v2), the dot
+ *   ((+0 + a0*c0) + a1*c1) + a2*c2 (the +0 start is the reference's reduction:
+ *   products that are all -0 sum to +0), so angle(0, .) = 0.  feat is (b,n,k,C)
+ *   with channels_first = 0 and (b,C,k,n) -- the Conv2d layout of TFMR.py:71 --
+ *   with channels_first = 1.  Channels 0-5 are exact; 6-9 up to the device's
+ *   atan2f / sqrtf.
+ * ------------------------------------------------------------------------- */
+int pcr_fps(const float *xyz, const int32_t *start, int32_t b, int32_t n, int32_t m, int32_t *idx,
+            pcr_stream_t stream);
+int pcr_ball_query(const float *xyz, const float *query, int32_t b, int32_t n, int32_t q, float r2,
+                   int32_t k, int32_t *idx, int32_t *count, pcr_stream_t stream);
+int pcr_group_ppf(const float *xyz, const float *normals, int32_t b, int32_t n, float r2, int32_t k,
+                  int32_t channels_first, float *feat, int32_t *idx, pcr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

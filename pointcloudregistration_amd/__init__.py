@@ -5,7 +5,17 @@ the C ABI in include/pcr_api.h (libpcr.so), with host-side mirrors of the
 reference's operator interfaces:
 
   nndistance     torch_nndistance.nnd / NNDFunction / torch_nndistance_aten
+  grouping       fps / gather_points / ball_query / sample_and_group of ROPNet's
+                 model_utils and NgeNet's process, and the fused PPF group
 """
 from ._lib import PcrError, load as load_library  # noqa: F401
 
-__all__ = ["PcrError", "load_library"]
+__all__ = ["PcrError", "load_library", "grouping"]
+
+
+def __getattr__(name):
+    # the op modules import torch; the package itself (ABI loader) does not
+    if name == "grouping":
+        import importlib
+        return importlib.import_module(".grouping", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

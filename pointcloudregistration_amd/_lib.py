@@ -99,6 +99,9 @@ SIGNATURES = {
     "pcr_hybrid_search": [_p, _i32, _i32, _p, _f64, _i32, _p, _p, _p, _p],
     "pcr_estimate_normals": [_p, _i32, _i32, _p, _f64, _i32, _p, _p, _p],
     "pcr_compute_fpfh": [_p, _p, _i32, _i32, _p, _f64, _i32, _p, _p, _p, _p],
+    "pcr_fps": [_p, _p, _i32, _i32, _i32, _p, _p],
+    "pcr_ball_query": [_p, _p, _i32, _i32, _i32, _f32, _i32, _p, _p, _p],
+    "pcr_group_ppf": [_p, _p, _i32, _i32, _f32, _i32, _i32, _p, _p, _p],
 }
 
 
