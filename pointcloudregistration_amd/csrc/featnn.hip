@@ -2583,38 +2583,28 @@ static int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax,
     const int NM = v.NM, ntn = v.ntn, ntm = v.ntm;
     const size_t ap = (size_t)P * ntn * NM * 64, bp = (size_t)P * ntm * NM * 64;  // f16x8
     const size_t nn_n = (size_t)P * ntn * 32, nn_m = (size_t)P * ntm * 32;
-    const size_t bytes =
-        16 * (ap + bp) + 4 * (3 * (nn_n + nn_m) + 9 * (size_t)P + 2 * (size_t)P * (Nmax + Mmax) + 19 * (size_t)P);
-    char *ws = (char *)workspace(2, bytes + 256);
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "feature_match: %s", pcr_last_error());
-    v.Ap = (f16x8 *)ws;
-    v.Bp = v.Ap + ap;
-    v.fnr = (float *)(v.Bp + bp);
-    v.gnr = v.fnr + nn_n;
-    v.fre = v.gnr + nn_m;
-    v.gre = v.fre + nn_n;
-    v.fct = v.gre + nn_m;
-    v.gct = v.fct + nn_n;
-    // [0,P): max|y|  [P,2P): max|x|  [2P,3P): the scale used  [3P,4P): cnt12  [4P,5P): cnt21
-    // [5P,6P): gemax  [6P,7P): femax  [7P,8P): fbc12  [8P,9P): fbc21 (feat_sample clears
-    // all but the scale)
-    v.gmax = (unsigned *)(v.gct + nn_m);
-    v.fmax = v.gmax + P;
-    v.mx = v.gmax + 2 * P;
-    v.cnt12 = (int *)(v.gmax + 3 * P);
-    v.cnt21 = v.cnt12 + P;
-    v.gemax = v.gmax + 5 * P;
-    v.femax = v.gmax + 6 * P;
-    v.fbc12 = (int *)(v.gmax + 7 * P);
-    v.fbc21 = v.fbc12 + P;
-    v.list12 = v.fbc21 + P;                    // per pair, stride Nmax
-    v.list21 = v.list12 + (size_t)P * Nmax;    // per pair, stride Mmax
-    v.fbl12 = v.list21 + (size_t)P * Mmax;     // per pair, stride Nmax
-    v.fbl21 = v.fbl12 + (size_t)P * Nmax;      // per pair, stride Mmax
-    unsigned *mxp = (unsigned *)(v.fbl21 + (size_t)P * Mmax);  // [P][2][zr] partial maxima (repair)
-    unsigned *smax = mxp + 2 * (size_t)P * 8;                     // [P] sample maxima
-    int *bad = (int *)(smax + P);                                  // [P] repair flags
-    v.cbias = (float *)(bad + P);                                  // [P] featnn_row9's B
+    const size_t pn = (size_t)P * Nmax, pm = (size_t)P * Mmax;
+    unsigned *mxp, *smax;
+    int *bad;
+    WsLayout l;
+    l.take(v.Ap, ap); l.take(v.Bp, bp);
+    l.take(v.fnr, nn_n); l.take(v.gnr, nn_m);
+    l.take(v.fre, nn_n); l.take(v.gre, nn_m);
+    l.take(v.fct, nn_n); l.take(v.gct, nn_m);
+    // nine [P] arrays, contiguous from gmax: max|y|, max|x|, the scale used, cnt12, cnt21,
+    // gemax, femax, fbc12, fbc21 (feat_sample clears all but the scale)
+    l.take(v.gmax, P); l.take(v.fmax, P); l.take(v.mx, P);
+    l.take(v.cnt12, P); l.take(v.cnt21, P);
+    l.take(v.gemax, P); l.take(v.femax, P);
+    l.take(v.fbc12, P); l.take(v.fbc21, P);
+    l.take(v.list12, pn); l.take(v.list21, pm);  // per pair, stride Nmax / Mmax
+    l.take(v.fbl12, pn); l.take(v.fbl21, pm);    // per pair, stride Nmax / Mmax
+    l.take(mxp, 2 * (size_t)P * 8);  // [P][2][zr] partial maxima (repair)
+    l.take(smax, P);                 // [P] sample maxima
+    l.take(bad, P);                  // [P] repair flags
+    l.take(v.cbias, P);              // [P] featnn_row9's B
+    PCR_REQUIRE(workspace_bind(kWsFeatPack_NndRagged, l, kWsSlack), PCR_ERR_NOMEM, "feature_match: %s",
+                pcr_last_error());
     prof_begin(s, kProfFeatPack);
     hipLaunchKernelGGL(feat_sample, dim3(P), dim3(256), 0, s, F, n_src, Nmax, G, n_tgt, Mmax, D, smax, v.gmax,
                        bad, P);
@@ -2669,10 +2659,10 @@ static int run_rescan(RescanArgs5 &ra, int P, int D, hipStream_t s) {
     // slices 0.575 / 0.489 / 0.471 ms per step)
     const int S = std::max(1, std::min(16, 4096 / std::max(P, 1)));
     if (S > 1) {
-        char *rw = (char *)workspace(6, (sizeof(double) + sizeof(int)) * (size_t)P * 2 * ra.cap * S + 64);
-        PCR_REQUIRE(rw, PCR_ERR_NOMEM, "feature_match: %s", pcr_last_error());
-        ra.sd = (double *)rw;
-        ra.sj = (int *)(ra.sd + (size_t)P * 2 * ra.cap * S);
+        WsLayout l;
+        l.take(ra.sd, (size_t)P * 2 * ra.cap * S);
+        l.take(ra.sj, (size_t)P * 2 * ra.cap * S);
+        PCR_REQUIRE(workspace_bind(kWsFeatRescan, l, kWsSlack), PCR_ERR_NOMEM, "feature_match: %s", pcr_last_error());
     }
     const dim3 rg(P, 2, S);
     if (getenv("PCR_RESCAN_DEBUG")) {  // diagnostic: the per-pair list lengths (host sync)
@@ -2724,10 +2714,10 @@ static int feature_match_v5(const float *F, const float *G, int P, int Nmax, int
     d.ctbits = 1;
     while ((1 << d.ctbits) < ntm) ++d.ctbits;
     const size_t cpn = (size_t)P * nrb * ntm * 32;
-    char *cw = (char *)workspace(11, cpn * 8 + 64);
-    PCR_REQUIRE(cw, PCR_ERR_NOMEM, "feature_match: %s", pcr_last_error());
-    d.cp1 = (float *)cw;
-    d.cp2 = d.cp1 + cpn;
+    WsLayout l;
+    l.take(d.cp1, cpn);
+    l.take(d.cp2, cpn);
+    PCR_REQUIRE(workspace_bind(kWsFeatDualCols, l, kWsSlack), PCR_ERR_NOMEM, "feature_match: %s", pcr_last_error());
     d.cpi = nullptr;
     const long long nblk = 8LL * nrb * cdiv(P, 8);  // XCD-aware 1-D grid
     PCR_REQUIRE(nblk < (1LL << 31), PCR_ERR_ARG, "feature_match: grid too large");
@@ -2927,28 +2917,28 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
     const size_t pr = (size_t)P * std::max(Nmax, Mmax);
     const int fsl = list_slices(P);
     const size_t pt = fsl > 1 ? (size_t)fsl * pr : 0;  // the sliced 3-term screens' partials
-    const size_t bytes = 8 * pn + 4 * pn + 16 * pm + 8 * (pm + P) + 8 * pm + 4 * (pn + P) + 8 * (size_t)P + 4 * pn + 16 +
-                         16 * (pl + pr + pt) + 4 * pb + 16;
-
-    bool fresh = false;
-    char *ws = (char *)workspace(33, bytes + 256, &fresh);
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "feature_corres: %s", pcr_last_error());
     MutArgs ma;
-    double *v12 = (double *)ws;
-    float *e12 = (float *)(v12 + pn);
-    float4 *wq = reinterpret_cast<float4 *>(((uintptr_t)(e12 + pn) + 15) & ~(uintptr_t)15);
-    ma.used = (int *)(wq + pm);
-    ma.pos = ma.used + pm + P;
-    ma.jlist = ma.pos + pm + P;
-    int *nn21x = ma.jlist + pm;
-    ma.flag = nn21x + pm;
-    ma.nj = ma.flag + pn + P;
-    int *zero = ma.nj + P;
-    int32_t *nns = zero + P;
-    uint4 *blist = reinterpret_cast<uint4 *>(((uintptr_t)(nns + pn) + 15) & ~(uintptr_t)15);
-    uint4 *rec = blist + pl;
-    uint4 *part = rec + pr;
-    int *bcnt = reinterpret_cast<int *>(part + pt);
+    double *v12;
+    float *e12;
+    float4 *wq;
+    int *nn21x, *zero, *bcnt;
+    int32_t *nns;
+    uint4 *blist, *rec, *part;
+    WsLayout l;  // pcr_featmut_debug_copy's readers go by these offsets
+    l.take(v12, pn); l.take(e12, pn);
+    l.take(wq, pm);  // 16-byte aligned
+    l.take(ma.used, pm + P); l.take(ma.pos, pm + P);
+    l.take(ma.jlist, pm); l.take(nn21x, pm);
+    l.take(ma.flag, pn + P);
+    l.take(ma.nj, P); l.take(zero, P);
+    l.take(nns, pn);
+    l.take(blist, pl);  // 16-byte aligned
+    l.take(rec, pr); l.take(part, pt);
+    l.take(bcnt, pb);
+    bool fresh = false;
+    // + 32: the tail also keeps 16 bytes per round-up (wq, blist) beyond the layout's own padding
+    PCR_REQUIRE(workspace_bind(kWsFeatMutual, l, kWsSlack + 32, &fresh), PCR_ERR_NOMEM, "feature_corres: %s",
+                pcr_last_error());
     const bool one = v.S <= 2 && feat_one_term();
     // (the regroup keeps a pair's per-step prefix in LDS)
     const bool use9 = one && feat_row9() && std::max(ntm, ntn) / 2 <= kRegroupMaxSteps;
@@ -3126,7 +3116,7 @@ int feature_corres_impl(const float *F, const float *G, int P, int Nmax, int Mma
         return feature_corres_v5(F, G, P, Nmax, Mmax, D, n_src, n_tgt, mutual, ransac_n, nn12, corres,
                                  n_corres, s);
     // 64 < D <= 128: both directions from the f32 screen, then the filter
-    int32_t *nn21 = (int32_t *)workspace(34, sizeof(int32_t) * (size_t)P * Mmax + 64);
+    int32_t *nn21 = (int32_t *)workspace(kWsFeatNn21, sizeof(int32_t) * (size_t)P * Mmax + 64);
     PCR_REQUIRE(nn21, PCR_ERR_NOMEM, "feature_corres: %s", pcr_last_error());
     int rc = feature_match_f32(F, G, P, Nmax, Mmax, D, n_src, n_tgt, nn12, nn21, s);
     if (rc != PCR_OK) return rc;
@@ -3144,7 +3134,7 @@ int feature_match_impl(const float *F, const float *G, int P, int Nmax, int Mmax
 int corres_impl(const int32_t *nn12, const int32_t *nn21, const int32_t *n_src,
                 const int32_t *n_tgt, int P, int Nmax, int Mmax, int mutual, int ransac_n,
                 int32_t *corres, int32_t *n_corres, hipStream_t s) {
-    int *scratch = (int *)workspace(3, sizeof(int) * (size_t)P * (Nmax + 1));
+    int *scratch = (int *)workspace(kWsCorres, sizeof(int) * (size_t)P * (Nmax + 1));
     PCR_REQUIRE(scratch, PCR_ERR_NOMEM, "corres: %s", pcr_last_error());
     hipLaunchKernelGGL(corres_build, dim3(P), dim3(1024), 0, s, nn12, nn21, n_src, n_tgt, Nmax, Mmax,
                        mutual, ransac_n, scratch, corres, n_corres);
@@ -3181,7 +3171,7 @@ extern "C" int pcr_feature_correspondences(const float *src_feat, const float *t
     hipStream_t s = pcr::as_stream(stream);
     if (Mmax == 0) {  // no target: nn12 = 0 (the reference loop never runs), no mutual pair
         PCR_HIP_CHECK(hipMemsetAsync(nn12, 0, sizeof(int32_t) * (size_t)P * Nmax, s));
-        int32_t *nn21 = (int32_t *)pcr::workspace(34, 64);
+        int32_t *nn21 = (int32_t *)pcr::workspace(pcr::kWsFeatNn21, 64);
         PCR_REQUIRE(nn21, PCR_ERR_NOMEM, "feature_corres: %s", pcr_last_error());
         return pcr::corres_impl(nn12, nn21, n_src, n_tgt, P, Nmax, 0, mutual_filter, ransac_n, corres,
                                 n_corres, s);
@@ -3194,7 +3184,7 @@ extern "C" int pcr_feature_correspondences(const float *src_feat, const float *t
 // nn21x | flag | nj, feature_corres_v5's layout) of the last call to dst
 extern "C" int pcr_featmut_debug_copy(void *dst, int64_t bytes, pcr_stream_t stream) {
     pcr::clear_error();
-    void *src = pcr::workspace(33, 16);
+    void *src = pcr::workspace(pcr::kWsFeatMutual, 16);
     PCR_REQUIRE(src && dst && bytes >= 0, PCR_ERR_ARG, "featmut_debug_copy: bad arguments");
     PCR_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, pcr::as_stream(stream)));
     return PCR_OK;

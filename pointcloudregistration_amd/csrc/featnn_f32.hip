@@ -342,17 +342,20 @@ int feature_match_f32(const float *F, const float *G, int P, int Nmax, int Mmax,
     const int ntn = cdiv(Nmax, 32), ntm = cdiv(Mmax, 32) + 8;  // +8 padded (+inf) tiles
     const size_t ap = (size_t)P * ntn * S2a * 64, bp = (size_t)P * ntm * S2a * 64;
     const size_t nn_n = (size_t)P * ntn * 32, nn_m = (size_t)P * ntm * 32;
-    const size_t bytes = 4 * (ap + bp + nn_n + nn_m + 2 * (size_t)P + 2 + (size_t)P * (Nmax + Mmax));
-    char *ws = (char *)workspace(2, bytes + 256);
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "feature_match: %s", pcr_last_error());
-    float *Ap = (float *)ws;
-    float *Bp = Ap + ap;
-    float *fnr = Bp + bp;
-    float *gnr = fnr + nn_n;
-    unsigned *gmax = (unsigned *)(gnr + nn_m);  // [0,P): max|g|  [P,2P): max|f|
-    int *list_count = (int *)(gmax + 2 * P);
-    int *list = list_count + 2;
-    int *list21 = list + (size_t)P * Nmax;
+    float *Ap, *Bp, *fnr, *gnr;
+    unsigned *gmax;
+    int *list_count, *list, *list21;
+    WsLayout l;
+    l.take(Ap, ap);
+    l.take(Bp, bp);
+    l.take(fnr, nn_n);
+    l.take(gnr, nn_m);
+    l.take(gmax, 2 * (size_t)P);  // [0,P): max|g|  [P,2P): max|f|
+    l.take(list_count, 2);        // right behind gmax: one memset clears both
+    l.take(list, (size_t)P * Nmax);
+    l.take(list21, (size_t)P * Mmax);
+    PCR_REQUIRE(workspace_bind(kWsFeatPack_NndRagged, l, kWsSlack), PCR_ERR_NOMEM, "feature_match: %s",
+                pcr_last_error());
     PCR_HIP_CHECK(hipMemsetAsync(gmax, 0, sizeof(unsigned) * 2 * P + 2 * sizeof(int), s));
     hipLaunchKernelGGL(feat_pack_aug, dim3(ntn, P), dim3(64), 0, s, F, n_src, Nmax, D, S2a, ntn, 0,
                        Ap, fnr, gmax + P);
@@ -365,11 +368,11 @@ int feature_match_f32(const float *F, const float *G, int P, int Nmax, int Mmax,
     d.n_src = n_src; d.n_tgt = n_tgt; d.Nmax = Nmax; d.Mmax = Mmax; d.ntn = ntn; d.ntm = ntm;
     d.nrb = cdiv(ntn, 8); d.nn12 = nn12; d.list12 = list; d.count12 = list_count;
     const size_t cpn = (size_t)P * d.nrb * ntm * 32;
-    char *cw = (char *)workspace(11, cpn * 12 + 64);
-    PCR_REQUIRE(cw, PCR_ERR_NOMEM, "feature_match: %s", pcr_last_error());
-    d.cp1 = (float *)cw;
-    d.cp2 = d.cp1 + cpn;
-    d.cpi = (int *)(d.cp2 + cpn);
+    WsLayout lc;
+    lc.take(d.cp1, cpn);
+    lc.take(d.cp2, cpn);
+    lc.take(d.cpi, cpn);
+    PCR_REQUIRE(workspace_bind(kWsFeatDualCols, lc, kWsSlack), PCR_ERR_NOMEM, "feature_match: %s", pcr_last_error());
     const dim3 g(d.nrb, P);
     prof_begin(s, kProfFeatScreen);
     {

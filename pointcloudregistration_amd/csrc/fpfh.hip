@@ -514,7 +514,7 @@ __global__ __launch_bounds__(64) void fpfh_kernel(FeatArgs a) {
 // ---- host ------------------------------------------------------------------
 
 int run_search(const float *xyz, int P, int N, const int32_t *n, double r, int K, hipStream_t s,
-               int ws_grid, int ws_lists, SearchArgs &a) {
+               WsSlot ws_grid, WsSlot ws_lists, SearchArgs &a) {
     PCR_REQUIRE(r > 0.0 && r < 1e300, PCR_ERR_ARG, "hybrid search: radius must be finite and > 0");
     PCR_REQUIRE(K >= 1 && K <= kMaxNN, PCR_ERR_ARG, "hybrid search: max_nn must be in [1, %d]", kMaxNN);
     PCR_REQUIRE(P <= 65535, PCR_ERR_ARG, "hybrid search: P=%d > 65535", P);
@@ -526,13 +526,13 @@ int run_search(const float *xyz, int P, int N, const int32_t *n, double r, int K
     a.thr = radius_thr(r);
     int rc = build_grids(xyz, n, P, N, r, s, ws_grid, a.g);
     if (rc != PCR_OK) return rc;
-    if (ws_lists >= 0) {
+    if (ws_lists != kWsNone) {
         const size_t pn = (size_t)P * N;
-        char *ws = (char *)workspace(ws_lists, pn * K * 12 + pn * 4 + 256);
-        PCR_REQUIRE(ws, PCR_ERR_NOMEM, "hybrid search: %s", pcr_last_error());
-        a.d2 = (double *)ws;
-        a.idx = (int32_t *)(ws + pn * K * 8);
-        a.cnt = (int32_t *)(ws + pn * K * 12);
+        WsLayout l;
+        l.take(a.d2, pn * K);
+        l.take(a.idx, pn * K);
+        l.take(a.cnt, pn);
+        PCR_REQUIRE(workspace_bind(ws_lists, l, kWsSlack), PCR_ERR_NOMEM, "hybrid search: %s", pcr_last_error());
     }
     hipLaunchKernelGGL(hybrid_search_kernel, dim3(N, P), dim3(kWave), 0, s, a);
     PCR_LAUNCH_CHECK();
@@ -554,7 +554,7 @@ extern "C" int pcr_hybrid_search(const float *xyz, int32_t P, int32_t Nmax, cons
     a.idx = idx;
     a.d2 = d2;
     a.cnt = counts;
-    return run_search(xyz, P, Nmax, n_pts, radius, max_nn, as_stream(stream), 24, -1, a);
+    return run_search(xyz, P, Nmax, n_pts, radius, max_nn, as_stream(stream), kWsRansacHypBits_FpfhGrid, kWsNone, a);
 }
 
 extern "C" int pcr_estimate_normals(const float *xyz, int32_t P, int32_t Nmax, const int32_t *n_pts,
@@ -567,7 +567,7 @@ extern "C" int pcr_estimate_normals(const float *xyz, int32_t P, int32_t Nmax, c
     PCR_REQUIRE(xyz && normals, PCR_ERR_ARG, "estimate_normals: null pointer");
     hipStream_t s = as_stream(stream);
     SearchArgs a{};
-    int rc = run_search(xyz, P, Nmax, n_pts, radius, max_nn, s, 24, 25, a);
+    int rc = run_search(xyz, P, Nmax, n_pts, radius, max_nn, s, kWsRansacHypBits_FpfhGrid, kWsRansacHdr_FpfhLists, a);
     if (rc != PCR_OK) return rc;
     NormalArgs b{xyz, n_pts, Nmax, max_nn, a.idx, a.cnt, prior_normals, normals};
     hipLaunchKernelGGL(normals_kernel, dim3((Nmax + 255) / 256, P), dim3(256), 0, s, b);
@@ -585,10 +585,10 @@ extern "C" int pcr_compute_fpfh(const float *xyz, const double *normals, int32_t
     PCR_REQUIRE(xyz && normals && fpfh, PCR_ERR_ARG, "compute_fpfh: null pointer");
     hipStream_t s = as_stream(stream);
     SearchArgs a{};
-    int rc = run_search(xyz, P, Nmax, n_pts, radius, max_nn, s, 24, 25, a);
+    int rc = run_search(xyz, P, Nmax, n_pts, radius, max_nn, s, kWsRansacHypBits_FpfhGrid, kWsRansacHdr_FpfhLists, a);
     if (rc != PCR_OK) return rc;
     if (!spfh) {
-        spfh = (double *)workspace(26, sizeof(double) * 33 * (size_t)P * Nmax);
+        spfh = (double *)workspace(kWsFpfhSpfh, sizeof(double) * 33 * (size_t)P * Nmax);
         PCR_REQUIRE(spfh, PCR_ERR_NOMEM, "compute_fpfh: %s", pcr_last_error());
     }
     FeatArgs f{xyz, normals, n_pts, Nmax, max_nn, a.idx, a.cnt, a.d2, spfh, fpfh, fpfh_f32};

@@ -490,13 +490,13 @@ __device__ inline GridDense grid_dense_lds_view(const GridBatch &gb, int p, char
 // f32 in slot perm_slot (a sweep in spatial order then reads its 64-point chunk
 // as one contiguous run instead of 64 scattered points)
 int spatial_order(const float *pts, const int32_t *n, int P, int Nmax, double cell, hipStream_t s,
-                  int ws_slot, const int32_t **order, const float **perm = nullptr, int perm_slot = -1);
+                  WsSlot ws_slot, const int32_t **order, const float **perm = nullptr, WsSlot perm_slot = kWsNone);
 
 // host: allocate (workspace slot) + build; returns PCR_OK or error
 // slots: the power of two >= Mmax (>= 256), times slot_num / 2 (3: 1.5x the
 // slots -- fewer collisions -- where the consumer's LDS has room for them)
 int build_grids(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double r,
-                hipStream_t s, int ws_slot, GridBatch &out, double cell_factor = 2.01, int slot_num = 2);
+                hipStream_t s, WsSlot ws_slot, GridBatch &out, double cell_factor = 2.01, int slot_num = 2);
 
 // host: like build_grids (slot_num as given), but one launch in which every
 // pair's workgroup chooses its layout: dense r-cell tables when
@@ -504,7 +504,7 @@ int build_grids(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double 
 // kDenseCellCap cells and kDenseMaxPoints points), else the hashed grid.  No
 // host synchronisation.  Needs grid_slots(Mmax, slot_num) <= 32768.
 int build_grids_auto(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double r, hipStream_t s,
-                     int ws_slot, GridBatch &out, int tab_bytes, int slot_num);
+                     WsSlot ws_slot, GridBatch &out, int tab_bytes, int slot_num);
 
 // host: PCR_ERR_ARG unless every pair of an auto-built batch took the dense
 // layout (synchronises the stream: for the forced-dense test switches only)

@@ -360,7 +360,7 @@ __global__ __launch_bounds__(1024) void spatial_order_kernel(const float *pts, c
 }  // namespace
 
 int spatial_order(const float *pts, const int32_t *n, int P, int Nmax, double cell, hipStream_t s,
-                  int ws_slot, const int32_t **order, const float **perm, int perm_slot) {
+                  WsSlot ws_slot, const int32_t **order, const float **perm, WsSlot perm_slot) {
     int32_t *o = (int32_t *)workspace(ws_slot, sizeof(int32_t) * (size_t)P * Nmax + 64);
     PCR_REQUIRE(o, PCR_ERR_NOMEM, "spatial_order: %s", pcr_last_error());
     float *pm = nullptr;
@@ -379,25 +379,22 @@ int spatial_order(const float *pts, const int32_t *n, int P, int Nmax, double ce
 }
 
 int build_grids(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double r, hipStream_t s,
-                int ws_slot, GridBatch &out, double cell_factor, int slot_num) {
+                WsSlot ws_slot, GridBatch &out, double cell_factor, int slot_num) {
     int S = 256;
     while (S < Mmax) S <<= 1;
     S = S / 2 * slot_num;
     const size_t cnt_b = sizeof(int) * (size_t)P * S;
-    const size_t start_b = sizeof(int) * (size_t)P * (S + 1);
-    const size_t pts_b = 16 * (size_t)P * (Mmax > 0 ? Mmax : 1);
-    char *ws = (char *)workspace(ws_slot, cnt_b + start_b + pts_b + 64);
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "grid workspace: %s", pcr_last_error());
     BuildArgs a;
+    WsLayout l;
+    l.take(a.cnt, (size_t)P * S);
+    l.take(a.start, (size_t)P * (S + 1));
+    l.take(a.pts, (size_t)P * (Mmax > 0 ? Mmax : 1));  // 16-byte aligned
+    PCR_REQUIRE(workspace_bind(ws_slot, l, kWsSlack), PCR_ERR_NOMEM, "grid workspace: %s", pcr_last_error());
     a.tgt = tgt;
     a.n_tgt = n_tgt;
     a.Mmax = Mmax;
     a.S = S;
     a.cell = cell_factor * r;
-    a.cnt = (int *)ws;
-    a.start = (int *)(ws + cnt_b);
-    size_t off = (cnt_b + start_b + 15) & ~size_t(15);
-    a.pts = (float4 *)(ws + off);
     if (S <= kLdsSlots) {
         PCR_HIP_CHECK(hipFuncSetAttribute((const void *)grid_build_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)(sizeof(int) * (kLdsSlots + 1))));
@@ -422,29 +419,25 @@ int build_grids(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double 
 }
 
 int build_grids_auto(const float *tgt, const int32_t *n_tgt, int P, int Mmax, double r, hipStream_t s,
-                     int ws_slot, GridBatch &out, int tab_bytes, int slot_num) {
+                     WsSlot ws_slot, GridBatch &out, int tab_bytes, int slot_num) {
     const int S = grid_slots(Mmax, slot_num);
     PCR_REQUIRE(S <= kLdsSlots && tab_bytes >= 16 && tab_bytes % 16 == 0, PCR_ERR_ARG,
                 "grid: auto layout with %d slots, %d table bytes", S, tab_bytes);
-    const size_t start_b = (sizeof(int) * (size_t)P * (S + 1) + 15) & ~size_t(15);
-    const size_t pts_b = 16 * (size_t)P * (Mmax > 0 ? Mmax : 1);
-    const size_t hdr_b = (sizeof(GridHdr) * (size_t)P + 15) & ~size_t(15);
-    const size_t tab_b = (size_t)P * tab_bytes;
-    char *ws = (char *)workspace(ws_slot, start_b + pts_b + hdr_b + tab_b + 64);
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "grid workspace: %s", pcr_last_error());
     BuildArgs a;
+    DenseArgs d;
+    WsLayout l;
+    l.take(a.start, (size_t)P * (S + 1));
+    l.take(a.pts, (size_t)P * (Mmax > 0 ? Mmax : 1));  // 16-byte aligned
+    l.take(d.hdr, P);
+    l.take(d.tab, (size_t)P * tab_bytes, 16);
+    PCR_REQUIRE(workspace_bind(ws_slot, l, kWsSlack), PCR_ERR_NOMEM, "grid workspace: %s", pcr_last_error());
     a.tgt = tgt;
     a.n_tgt = n_tgt;
     a.Mmax = Mmax;
     a.S = S;
     a.cell = 2.01 * r;
     a.cnt = nullptr;
-    a.start = (int *)ws;
-    a.pts = (float4 *)(ws + start_b);
-    DenseArgs d;
     d.dcell = kDenseCellFactor * r;
-    d.hdr = (GridHdr *)(ws + start_b + pts_b);
-    d.tab = ws + start_b + pts_b + hdr_b;
     d.tab_bytes = tab_bytes;
     const size_t sm = sizeof(int) * (size_t)kAutoLdsInts;
     PCR_HIP_CHECK(hipFuncSetAttribute((const void *)grid_build_auto, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -514,8 +507,9 @@ extern "C" int pcr_radius_nn(const float *tgt_xyz, int32_t P, int32_t Mmax, cons
     pcr::GridBatch g{};
     int rc;
     const bool can = Mmax <= pcr::kDenseMaxPoints && pcr::grid_slots(Mmax, 2) <= 32768;
-    if ((want_dense || want_auto) && can) rc = pcr::build_grids_auto(tgt_xyz, n_tgt, P, Mmax, r, s, 10, g, 32 * 1024, 2);
-    else rc = pcr::build_grids(tgt_xyz, n_tgt, P, Mmax, r, s, 10, g);
+    const pcr::WsSlot slot = pcr::kWsIcpPartials_RadiusNnGrid;
+    if ((want_dense || want_auto) && can) rc = pcr::build_grids_auto(tgt_xyz, n_tgt, P, Mmax, r, s, slot, g, 32 * 1024, 2);
+    else rc = pcr::build_grids(tgt_xyz, n_tgt, P, Mmax, r, s, slot, g);
     if (rc != PCR_OK) return rc;
     if (want_dense) {
         rc = pcr::require_all_dense(g, P, s, "radius_nn");

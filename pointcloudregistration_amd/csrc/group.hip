@@ -366,7 +366,7 @@ extern "C" int pcr_fps(const float *xyz, const int32_t *start, int32_t b, int32_
     } else if (n <= kFpsRegPoints) {
         hipLaunchKernelGGL((fps_kernel<8, false>), dim3(b), dim3(kFpsThreads), 0, s, a);
     } else {
-        a.over = (float *)pcr::workspace(5, sizeof(float) * (size_t)b * (n - kFpsRegPoints));
+        a.over = (float *)pcr::workspace(pcr::kWsFpsOver_PpfIdx, sizeof(float) * (size_t)b * (n - kFpsRegPoints));
         PCR_REQUIRE(a.over, PCR_ERR_NOMEM, "fps: %s", pcr_last_error());
         hipLaunchKernelGGL((fps_kernel<8, true>), dim3(b), dim3(kFpsThreads), 0, s, a);
     }
@@ -400,7 +400,7 @@ extern "C" int pcr_group_ppf(const float *xyz, const float *normals, int32_t b, 
     PCR_REQUIRE(xyz && feat, PCR_ERR_ARG, "group_ppf: null pointer");
     hipStream_t s = pcr::as_stream(stream);
     if (!idx) {
-        idx = (int32_t *)pcr::workspace(5, sizeof(int32_t) * (size_t)b * n * k);
+        idx = (int32_t *)pcr::workspace(pcr::kWsFpsOver_PpfIdx, sizeof(int32_t) * (size_t)b * n * k);
         PCR_REQUIRE(idx, PCR_ERR_NOMEM, "group_ppf: %s", pcr_last_error());
     }
     const int rc = launch_ball_query(xyz, xyz, b, n, n, r2, k, idx, nullptr, s);

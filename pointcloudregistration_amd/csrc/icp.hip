@@ -631,7 +631,7 @@ int icp_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax, cons
     if (a.d > 0.0) {
         int rc = PCR_OK;
         if (grid_in) a.grid = *grid_in;  // built by the caller (pcr_pipeline_step's side stream)
-        else rc = build_grids(tgt, n_tgt, P, Mmax, a.d, s, 7, a.grid);
+        else rc = build_grids(tgt, n_tgt, P, Mmax, a.d, s, kWsIcpGrid, a.grid);
         if (rc != PCR_OK) return rc;
         if (Nmax > 0) {
             // any spatial order serves (it only groups a wave's queries): the
@@ -640,7 +640,7 @@ int icp_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax, cons
                 a.order = order_in;
                 a.srcp = perm_in;
             } else {
-                rc = spatial_order(src, n_src, P, Nmax, a.grid.cell, s, 14, &a.order, &a.srcp, 35);
+                rc = spatial_order(src, n_src, P, Nmax, a.grid.cell, s, kWsIcpOrder, &a.order, &a.srcp, kWsIcpPerm);
                 if (rc != PCR_OK) return rc;
             }
         }
@@ -687,15 +687,15 @@ int icp_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax, cons
     if (two_phase) a.thr_active = grid2 / 4;  // phase 2: >= 4 workgroups per listed pair
     // working copy, by position
     const size_t nm = (size_t)(Nmax > 0 ? Nmax : 1);
-    char *ws = (char *)workspace(8, sizeof(double) * 3 * (size_t)P * nm + 64);
+    char *ws = (char *)workspace(kWsIcpPoints, sizeof(double) * 3 * (size_t)P * nm + 64);
     PCR_REQUIRE(ws, PCR_ERR_NOMEM, "icp: %s", pcr_last_error());
     a.P3 = (double *)ws;
-    a.cst = (int4 *)workspace(38, sizeof(int4) * (size_t)P * nm + 64);
+    a.cst = (int4 *)workspace(kWsIcpCst, sizeof(int4) * (size_t)P * nm + 64);
     PCR_REQUIRE(a.cst, PCR_ERR_NOMEM, "icp: %s", pcr_last_error());
     bool *icp_dirty = nullptr;
     if (a.G > 1 || two_phase) {
         const int gp = two_phase ? a.gmax2 : a.G;  // partial slots per pair
-        char *cw = (char *)workspace(10, sizeof(XPart) * 2 * (size_t)gp * (size_t)P + 64);
+        char *cw = (char *)workspace(kWsIcpPartials_RadiusNnGrid, sizeof(XPart) * 2 * (size_t)gp * (size_t)P + 64);
         PCR_REQUIRE(cw, PCR_ERR_NOMEM, "icp: %s", pcr_last_error());
         a.part = (XPart *)cw;
         // barriers in a slot of their own, zeroed when allocated: every launch
@@ -709,12 +709,12 @@ int icp_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax, cons
         // arrivals behind: the call after any failed one in this (device,
         // context) re-zeroes.
         bool fresh = false;
-        a.bar = (unsigned *)workspace(39, sizeof(unsigned) * nb, &fresh);
+        a.bar = (unsigned *)workspace(kWsIcpBarrier, sizeof(unsigned) * nb, &fresh);
         PCR_REQUIRE(a.bar, PCR_ERR_NOMEM, "icp: %s", pcr_last_error());
         // the slot's dirty flag (per device and workspace context, as the slot
         // itself) is set while a call's launches are being issued: a call that
         // returned an error in between leaves it set for the next one here
-        icp_dirty = workspace_dirty(39);
+        icp_dirty = workspace_dirty(kWsIcpBarrier);
         PCR_REQUIRE(icp_dirty, PCR_ERR_ARG, "icp: no workspace slot");
         if (fresh || *icp_dirty) PCR_HIP_CHECK(hipMemsetAsync(a.bar, 0, sizeof(unsigned) * nb, s));
         *icp_dirty = false;
@@ -725,16 +725,16 @@ int icp_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax, cons
     a.timing = nullptr;
     const bool want_timing = getenv("PCR_ICP_TIMING") != nullptr;
     if (want_timing) {
-        a.timing = (unsigned long long *)workspace(12, sizeof(unsigned long long) * 12 * (size_t)P);
+        a.timing = (unsigned long long *)workspace(kWsIcpTiming, sizeof(unsigned long long) * 12 * (size_t)P);
         PCR_REQUIRE(a.timing, PCR_ERR_NOMEM, "icp timing: %s", pcr_last_error());
         PCR_HIP_CHECK(hipMemsetAsync(a.timing, 0, sizeof(unsigned long long) * 12 * (size_t)P, s));
     }
     if (two_phase) {
-        char *tw = (char *)workspace(37, sizeof(int) * (2 + (size_t)P) + sizeof(double) * kSave * (size_t)P + 64);
-        PCR_REQUIRE(tw, PCR_ERR_NOMEM, "icp: %s", pcr_last_error());
-        a.save = (double *)tw;
-        a.ctl = (int *)(a.save + kSave * (size_t)P);
-        a.list = a.ctl + 2;
+        WsLayout l;
+        l.take(a.save, kSave * (size_t)P);
+        l.take(a.ctl, 2);
+        l.take(a.list, P);
+        PCR_REQUIRE(workspace_bind(kWsIcpTail, l, kWsSlack), PCR_ERR_NOMEM, "icp: %s", pcr_last_error());
         PCR_HIP_CHECK(hipMemsetD32Async(a.ctl, P, 1, s));       // pairs iterating
         PCR_HIP_CHECK(hipMemsetAsync(a.ctl + 1, 0, sizeof(int), s));  // none listed
     }

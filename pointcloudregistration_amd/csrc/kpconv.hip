@@ -221,18 +221,6 @@ __global__ void gs_emit(GsArgs a, const int *outr, int total, const int *list, c
 
 inline unsigned nbits(u64 x) { return x ? 64u - (unsigned)__builtin_clzll(x) : 0u; }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// carve a workspace slot into aligned sub-buffers
-struct Carver {
-    size_t used = 0;
-    template <class T> size_t take(size_t count) {
-        const size_t at = used;
-        used = align256(used + sizeof(T) * (count > 0 ? count : 1));
-        return at;
-    }
-};
-
 // ---------------------------------------------------------------------------
 // radius neighbours
 // ---------------------------------------------------------------------------
@@ -434,22 +422,16 @@ int rn_prepare(const float *q, int nq, const float *s, int ns, const int32_t *qb
     while (S < 2 * ns) S <<= 1;
     a.S = S;
     a.ibits = (int)nbits((u64)(ns > 0 ? ns : 1));
-    Carver c;
-    const size_t o_off = c.take<int>(2 * (nb + 1)), o_hdr = c.take<u64>(3), o_h = c.take<int>(S + 1),
-                 o_st = c.take<int>(S + 1), o_pts = c.take<float4>(ns), o_cnt = c.take<int>(nq),
-                 o_offs = c.take<unsigned>(nq + 1), o_bl = c.take<int>(nq), o_tl = c.take<int>(nq);
-    char *ws = (char *)workspace(18, c.used);
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "radius_neighbors: %s", pcr_last_error());
-    int *dev_off = (int *)(ws + o_off);
+    int *dev_off;
+    WsLayout l(256);
+    l.take(dev_off, 2 * (nb + 1)); l.take(a.total, 3);
+    l.take(a.hcnt, S + 1); l.take(a.start, S + 1); l.take(a.cell_pts, ns);
+    l.take(a.counts, nq); l.take(a.offs, nq + 1);
+    l.take(a.blist, nq); l.take(a.tlist, nq);
+    PCR_REQUIRE(workspace_bind(kWsNeighbors, l), PCR_ERR_NOMEM, "radius_neighbors: %s", pcr_last_error());
     a.qoff = dev_off; a.soff = dev_off + nb + 1;
-    a.total = (u64 *)(ws + o_hdr);
     a.bad = (int *)(a.total + 1); a.maxcnt = a.bad + 1;
     a.bcnt = (int *)(a.total + 2); a.tcnt = a.bcnt + 1;
-    a.blist = (int *)(ws + o_bl); a.tlist = (int *)(ws + o_tl);
-    a.hcnt = (int *)(ws + o_h); a.start = (int *)(ws + o_st);
-    a.cell_pts = (float4 *)(ws + o_pts);
-    a.counts = (int *)(ws + o_cnt);
-    a.offs = (const unsigned *)(ws + o_offs);
     std::vector<int> offs(P.qoff);
     offs.insert(offs.end(), P.soff.begin(), P.soff.end());
     PCR_HIP_CHECK(hipMemcpyAsync(dev_off, offs.data(), sizeof(int) * offs.size(), hipMemcpyHostToDevice, st));
@@ -460,7 +442,7 @@ int rn_prepare(const float *q, int nq, const float *s, int ns, const int32_t *qb
     PCR_HIP_CHECK(rocprim::exclusive_scan(nullptr, tb2, (const int *)a.counts, (unsigned *)a.offs, 0u,
                                           (size_t)nq + 1, rocprim::plus<unsigned>(), st));
     tb = tb > tb2 ? tb : tb2;
-    P.tmp = workspace(19, tb);
+    P.tmp = workspace(kWsNeighborsTmp, tb);
     P.tmp_bytes = tb;
     PCR_REQUIRE(P.tmp, PCR_ERR_NOMEM, "radius_neighbors: %s", pcr_last_error());
     if (a.ic > 0.0 && ns > 0) {
@@ -577,28 +559,20 @@ extern "C" int pcr_grid_subsample(const float *points, int32_t n, const int32_t 
     for (int b = 0; b < nb; ++b) out_batch_len[b] = 0;
     if (N == 0) return PCR_OK;
     hipStream_t st = as_stream(stream);
-    Carver c;
-    const size_t o_off = c.take<int>(nb + 1), o_org = c.take<float>(3 * nb), o_nxy = c.take<u64>(2 * nb),
-                 o_mk = c.take<u64>(2), o_key = c.take<u64>(N), o_bat = c.take<int>(N),
-                 o_ck = c.take<u64>(N), o_ck2 = c.take<u64>(N), o_iota = c.take<int>(N),
-                 o_v = c.take<int>(N), o_v2 = c.take<int>(N), o_head = c.take<unsigned char>(N),
-                 o_start = c.take<int>(N + 1), o_mark = c.take<int>(N), o_list = c.take<int>(N),
-                 o_okey = c.take<u64>(N), o_obat = c.take<int>(N), o_outr = c.take<int>(N),
-                 o_cnt = c.take<int>(2);
-    char *ws = (char *)workspace(16, c.used);
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "grid_subsample: %s", pcr_last_error());
     GsArgs a;
+    u64 *ck, *ck2, *okey;
+    int *iota, *v, *v2, *start, *mark, *list, *obat, *outr, *dcnt;
+    unsigned char *head;
+    WsLayout l(256);
+    l.take(a.off, nb + 1); l.take(a.origin, 3 * nb); l.take(a.nxy, 2 * nb); l.take(a.maxkey, 2);
+    l.take(a.key, N); l.take(a.bat, N);
+    l.take(ck, N); l.take(ck2, N); l.take(iota, N); l.take(v, N); l.take(v2, N);
+    l.take(head, N); l.take(start, N + 1); l.take(mark, N); l.take(list, N);
+    l.take(okey, N); l.take(obat, N); l.take(outr, N); l.take(dcnt, 2);
+    PCR_REQUIRE(workspace_bind(kWsSubsample, l), PCR_ERR_NOMEM, "grid_subsample: %s", pcr_last_error());
     a.pts = points; a.feat = fdim > 0 ? features : nullptr; a.n = N; a.fdim = fdim; a.nb = nb;
-    a.off = (int *)(ws + o_off); a.dl = dl;
-    a.origin = (float *)(ws + o_org); a.nxy = (u64 *)(ws + o_nxy);
-    a.maxkey = (u64 *)(ws + o_mk); a.bad = (int *)(a.maxkey + 1);
-    a.key = (u64 *)(ws + o_key); a.bat = (int *)(ws + o_bat);
-    u64 *ck = (u64 *)(ws + o_ck), *ck2 = (u64 *)(ws + o_ck2);
-    int *iota = (int *)(ws + o_iota), *v = (int *)(ws + o_v), *v2 = (int *)(ws + o_v2);
-    unsigned char *head = (unsigned char *)(ws + o_head);
-    int *start = (int *)(ws + o_start), *mark = (int *)(ws + o_mark), *list = (int *)(ws + o_list);
-    u64 *okey = (u64 *)(ws + o_okey);
-    int *obat = (int *)(ws + o_obat), *outr = (int *)(ws + o_outr), *dcnt = (int *)(ws + o_cnt);
+    a.dl = dl;
+    a.bad = (int *)(a.maxkey + 1);
 
     PCR_HIP_CHECK(hipMemcpyAsync((void *)a.off, off.data(), sizeof(int) * (nb + 1), hipMemcpyHostToDevice, st));
     PCR_HIP_CHECK(hipMemsetAsync(a.maxkey, 0, 2 * sizeof(u64), st));
@@ -622,7 +596,7 @@ extern "C" int pcr_grid_subsample(const float *points, int32_t n, const int32_t 
     tb = tb > t1 ? tb : t1;
     PCR_HIP_CHECK(rocprim::select(nullptr, t1, mark, list, dcnt + 1, (size_t)N, NonNeg(), st));
     tb = tb > t1 ? tb : t1;
-    void *tmp = workspace(17, tb);
+    void *tmp = workspace(kWsSubsampleTmp, tb);
     PCR_REQUIRE(tmp, PCR_ERR_NOMEM, "grid_subsample: %s", pcr_last_error());
     if (kbits + bbits <= 64) {
         hipLaunchKernelGGL(gs_compose, gN, blk, 0, st, a.key, a.bat, N, (int)kbits, ck, iota);
@@ -754,15 +728,15 @@ extern "C" int pcr_radius_neighbors(const float *queries, int32_t nq, const floa
         PCR_HIP_CHECK(rocprim::segmented_radix_sort_keys(nullptr, tb, (const u64 *)nullptr, (u64 *)nullptr,
                                                          (unsigned)total, (unsigned)nq, P.a.offs, P.a.offs + 1,
                                                          0u, ebit, st));
-        Carver c;
-        const size_t o_k = c.take<u64>(total), o_k2 = c.take<u64>(total), o_t = c.take<char>(tb);
-        char *ws = (char *)workspace(20, c.used);
-        PCR_REQUIRE(ws, PCR_ERR_NOMEM, "radius_neighbors: %s", pcr_last_error());
-        P.a.keys = (u64 *)(ws + o_k);
-        keys2 = (u64 *)(ws + o_k2);
+        char *sort_tmp;
+        WsLayout l(256);
+        l.take(P.a.keys, total);
+        l.take(keys2, total);
+        l.take(sort_tmp, tb);
+        PCR_REQUIRE(workspace_bind(kWsNeighborsKeys, l), PCR_ERR_NOMEM, "radius_neighbors: %s", pcr_last_error());
         hipLaunchKernelGGL(rn_query<true>, dim3((nq + 255) / 256), dim3(256), 0, st, P.a);
         PCR_LAUNCH_CHECK();
-        PCR_HIP_CHECK(rocprim::segmented_radix_sort_keys(ws + o_t, tb, (const u64 *)P.a.keys, keys2,
+        PCR_HIP_CHECK(rocprim::segmented_radix_sort_keys(sort_tmp, tb, (const u64 *)P.a.keys, keys2,
                                                          (unsigned)total, (unsigned)nq, P.a.offs, P.a.offs + 1,
                                                          0u, ebit, st));
         hipLaunchKernelGGL(rn_ties, dim3((nq + 255) / 256), dim3(256), 0, st, (const u64 *)keys2, P.a.offs,

@@ -853,30 +853,30 @@ inline int pow2_at_least(int n, int lo) {
     return S;
 }
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
+// offsets into the caller's scratch (K, M >= 1: no count is zero); the total is
+// ABI (pcr_ndp_chamfer_scratch_bytes)
 NcLayout nc_layout(int K, int M) {
     NcLayout L;
     const int n[2] = {M, K};
-    size_t o = 0;
-    L.hdr = o; o = up256(o + sizeof(NcHdr));
+    WsLayout w(256);
+    L.hdr = w.take<NcHdr>(1);
     for (int c = 0; c < 2; ++c) {
         L.S[c] = pow2_at_least(n[c], 256);
-        L.start[c] = o; o = up256(o + sizeof(int) * ((size_t)L.S[c] + 1));
-        L.pts[c] = o; o = up256(o + sizeof(float4) * (size_t)n[c]);
+        L.start[c] = w.take<int>((size_t)L.S[c] + 1);
+        L.pts[c] = w.take<float4>(n[c]);
     }
     for (int c = 0; c < 2; ++c) {
         L.L[c] = (n[c] + kLeaf - 1) / kLeaf;
         L.G[c] = (L.L[c] + kGrp - 1) / kGrp;
-        L.ord[c] = o; o = up256(o + sizeof(int) * (size_t)n[c]);
-        L.bpts[c] = o; o = up256(o + sizeof(float4) * (size_t)n[c]);
-        L.leaf[c] = o; o = up256(o + sizeof(NcBox) * (size_t)L.L[c]);
-        L.grp[c] = o; o = up256(o + sizeof(NcBox) * (size_t)L.G[c]);
+        L.ord[c] = w.take<int>(n[c]);
+        L.bpts[c] = w.take<float4>(n[c]);
+        L.leaf[c] = w.take<NcBox>(L.L[c]);
+        L.grp[c] = w.take<NcBox>(L.G[c]);
     }
-    L.cnt = o; o = up256(o + sizeof(int) * (size_t)std::max(L.S[0], L.S[1]));
-    L.fb = o; o = up256(o + sizeof(int) * ((size_t)K + M));
-    L.fbkey = o; o = up256(o + sizeof(unsigned long long) * ((size_t)K + M));
-    L.total = o;
+    L.cnt = w.take<int>(std::max(L.S[0], L.S[1]));
+    L.fb = w.take<int>((size_t)K + M);
+    L.fbkey = w.take<unsigned long long>((size_t)K + M);
+    L.total = w.bytes();
     return L;
 }
 

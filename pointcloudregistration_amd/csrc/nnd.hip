@@ -399,10 +399,10 @@ extern "C" int pcr_nnd_forward(const float *xyz1, const float *xyz2, int32_t b, 
     PCR_REQUIRE(2LL * b <= 65535, PCR_ERR_ARG, "nnd_forward: b=%d too large (max 32767)", b);
     if (a.split) {
         const size_t cells = (size_t)ys * 2 * b * nmax;
-        char *ws = (char *)pcr::workspace(0, cells * (sizeof(float) + sizeof(int32_t)));
-        PCR_REQUIRE(ws, PCR_ERR_NOMEM, "nnd_forward: %s", pcr_last_error());
-        a.pd = (float *)ws;
-        a.pj = (int32_t *)(ws + cells * sizeof(float));
+        pcr::WsLayout l;
+        l.take(a.pd, cells);
+        l.take(a.pj, cells);
+        PCR_REQUIRE(pcr::workspace_bind(pcr::kWsNndPartials, l), PCR_ERR_NOMEM, "nnd_forward: %s", pcr_last_error());
     }
     pcr::prof_begin(s, pcr::kProfNndFwd);
     if (small)
@@ -431,24 +431,22 @@ extern "C" int pcr_nnd_backward(const float *xyz1, const float *xyz2, const floa
     PCR_REQUIRE(2LL * b <= 65535, PCR_ERR_ARG, "nnd_backward: b=%d too large", b);
     hipStream_t s = pcr::as_stream(stream);
     const size_t bn = (size_t)b * n, bm = (size_t)b * m;
-    // workspace: cnt1[bm] cnt2[bn] start1[b*(m+1)] start2[b*(n+1)] uns1[bn] uns2[bm] srt1[bn] srt2[bm]
-    const size_t words = bm + bn + (size_t)b * (m + 1) + (size_t)b * (n + 1) + 2 * (bn + bm);
-    int *ws = (int *)pcr::workspace(1, words * sizeof(int));
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "nnd_backward: %s", pcr_last_error());
     BwdArgs a;
+    pcr::WsLayout l;
+    l.take(a.cnt1, bm);
+    l.take(a.cnt2, bn);
+    l.take(a.start1, (size_t)b * (m + 1));
+    l.take(a.start2, (size_t)b * (n + 1));
+    l.take(a.uns1, bn);
+    l.take(a.uns2, bm);
+    l.take(a.srt1, bn);
+    l.take(a.srt2, bm);
+    void *ws = pcr::workspace_bind(pcr::kWsNndBackward, l);
+    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "nnd_backward: %s", pcr_last_error());
     a.xyz1 = xyz1; a.xyz2 = xyz2; a.gd1 = gd1; a.gd2 = gd2; a.idx1 = idx1; a.idx2 = idx2;
     a.g1 = g1; a.g2 = g2; a.b = b; a.n = n; a.m = m;
     a.gate = pcr::current_gate();
-    int *p = ws;
-    a.cnt1 = p; p += bm;
-    a.cnt2 = p; p += bn;
-    a.start1 = p; p += (size_t)b * (m + 1);
-    a.start2 = p; p += (size_t)b * (n + 1);
-    a.uns1 = p; p += bn;
-    a.uns2 = p; p += bm;
-    a.srt1 = p; p += bn;
-    a.srt2 = p; p += bm;
-    PCR_HIP_CHECK(hipMemsetAsync(ws, 0, sizeof(int) * (bm + bn), s));
+    PCR_HIP_CHECK(hipMemsetAsync(ws, 0, sizeof(int) * (bm + bn), s));  // cnt1, cnt2
     const int nmax = n > m ? n : m;
     const dim3 g(cdiv(nmax > 0 ? nmax : 1, 256), 1, 2 * b);
     hipLaunchKernelGGL(bw_count, g, dim3(256), 0, s, a);

@@ -309,13 +309,13 @@ int nnd_forward_grid_xf(const float *xyz1, const float *src, const double *T, co
     while (S < a.nmax) S <<= 1;
     a.S = S;
     const size_t cells = 2 * (size_t)b, hc = cells * S, stc = cells * (S + 1), pc = cells * a.nmax;
-    char *ws = (char *)workspace(15, 4 * (cells + 2 * (size_t)b + hc + stc) + 16 * pc + 256);
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "nnd_forward (grid): %s", pcr_last_error());
-    a.pts = (float4 *)ws;
-    a.cell = (float *)(a.pts + pc);
-    a.flag = (int *)(a.cell + cells);
-    a.hcnt = a.flag + 2 * (size_t)b;
-    a.start = a.hcnt + hc;
+    WsLayout l;
+    l.take(a.pts, pc);
+    l.take(a.cell, cells);
+    l.take(a.flag, 2 * (size_t)b);
+    l.take(a.hcnt, hc);
+    l.take(a.start, stc);
+    PCR_REQUIRE(workspace_bind(kWsNndGrid, l, kWsSlack), PCR_ERR_NOMEM, "nnd_forward (grid): %s", pcr_last_error());
     a.dist[0] = dist1; a.dist[1] = dist2; a.idx[0] = idx1; a.idx[1] = idx2;
     a.gate = current_gate();
     a.cf = 0.6f;  // 0.4 / 0.5 / 0.6 / 0.8 / 1.0 x cbrt(V / n) measured

@@ -168,10 +168,11 @@ int nnd_ragged(const Scalar *xyz1, const Scalar *xyz2, int32_t b, int32_t n, int
     a.slice_len = rcdiv(rcdiv(nmax, slices), kRTile) * kRTile;
     a.slices = rcdiv(nmax, a.slice_len);
     const size_t cells = (size_t)a.slices * 2 * b * nmax;
-    char *ws = (char *)pcr::workspace(2, cells * (sizeof(Scalar) + sizeof(int32_t)));
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "nnd_forward_ragged: %s", pcr_last_error());
-    a.pd = (Scalar *)ws;
-    a.pj = (int32_t *)(ws + cells * sizeof(Scalar));
+    pcr::WsLayout l;
+    l.take(a.pd, cells);
+    l.take(a.pj, cells);
+    PCR_REQUIRE(pcr::workspace_bind(pcr::kWsFeatPack_NndRagged, l), PCR_ERR_NOMEM, "nnd_forward_ragged: %s",
+                pcr_last_error());
     hipLaunchKernelGGL(nnd_ragged_kernel<Scalar>, dim3(qtiles, a.slices, 2 * b), dim3(kRThreads), 0,
                        s, a);
     PCR_LAUNCH_CHECK();

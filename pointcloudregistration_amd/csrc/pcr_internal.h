@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/pcr_api.h"
+#include "workspace.h"
 
 namespace pcr {
 
@@ -16,10 +17,14 @@ void clear_error();
 // stay allocated until process exit so kernels still in flight on another
 // stream never see their scratch freed.  Mutex-guarded.  *fresh (optional) tells
 // whether the buffer was (re)allocated by this call (contents undefined).
-void *workspace(int slot, size_t bytes, bool *fresh = nullptr);
+// Slots have names (workspace.h); an integer literal does not compile.
+void *workspace(WsSlot slot, size_t bytes, bool *fresh = nullptr);
 // a flag kept beside the calling thread's (device, context) buffer of `slot`
 // (false at first): set by an owner whose launches may not all have gone in
-bool *workspace_dirty(int slot);
+bool *workspace_dirty(WsSlot slot);
+// a slot of l.bytes() + slack, with l's pointers bound to it; null (error set)
+// when the layout overflows or the slot cannot be had
+void *workspace_bind(WsSlot slot, const WsLayout &l, size_t slack = 0, bool *fresh = nullptr);
 
 // Chamfer NN (nnd.hip / nnd_grid.hip): the size rule of pcr_nnd_forward, and
 // its grid path; _xf forms set 0 as T (x) src (transform_kernel's rounding),

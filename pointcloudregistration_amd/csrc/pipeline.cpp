@@ -48,13 +48,13 @@ extern "C" int pcr_register_feature_ransac(const float *src_xyz, const float *tg
                 PCR_ERR_ARG, "register: null pointer");
     PCR_REQUIRE(P <= 65535, PCR_ERR_ARG, "register: P=%d > 65535", P);
     hipStream_t s = pcr::as_stream(stream);
-    // nn12 | nn21 | corres | n_corres
-    const size_t words = (size_t)P * Nmax + (size_t)P * Mmax + (size_t)P * Nmax * 2 + P;
-    int32_t *ws = (int32_t *)pcr::workspace(9, words * sizeof(int32_t));
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "register: %s", pcr_last_error());
-    int32_t *nn12 = ws, *nn21 = nn12 + (size_t)P * Nmax, *corres = nn21 + (size_t)P * Mmax;
-    int32_t *n_corres = corres + (size_t)P * Nmax * 2;
-    (void)nn21;
+    int32_t *nn12, *nn21, *corres, *n_corres;
+    pcr::WsLayout l;
+    l.take(nn12, (size_t)P * Nmax);
+    l.take(nn21, (size_t)P * Mmax);
+    l.take(corres, (size_t)P * Nmax * 2);
+    l.take(n_corres, P);
+    PCR_REQUIRE(pcr::workspace_bind(pcr::kWsRegister, l), PCR_ERR_NOMEM, "register: %s", pcr_last_error());
     int rc = PCR_OK;
     if (Mmax > 0 && Nmax > 0) {
         rc = pcr::feature_corres_impl(src_feat, tgt_feat, P, Nmax, Mmax, D, n_src, n_tgt,
@@ -131,11 +131,11 @@ extern "C" int pcr_pipeline_step(const pcr_pipeline_io *io, const pcr_ransac_par
         if (gr) {
             int r = pcr::build_ransac_grids(io->tgt_xyz, nullptr, P, M, rp->max_correspondence_distance, side, grid_r);
             if (r != PCR_OK) return r;
-            r = pcr::spatial_order(io->src_xyz, nullptr, P, N, grid_r.cell, side, 13, &order, &perm, 36);
+            r = pcr::spatial_order(io->src_xyz, nullptr, P, N, grid_r.cell, side, pcr::kWsRansacOrder, &order, &perm, pcr::kWsRansacPerm);
             if (r != PCR_OK) return r;
         }
         if (gi) {
-            int r = pcr::build_grids(io->tgt_xyz, nullptr, P, M, ip->max_correspondence_distance, side, 7, grid_i);
+            int r = pcr::build_grids(io->tgt_xyz, nullptr, P, M, ip->max_correspondence_distance, side, pcr::kWsIcpGrid, grid_i);
             if (r != PCR_OK) return r;
         }
         PCR_HIP_CHECK(hipEventRecord(ev_prep, side));

@@ -762,10 +762,10 @@ int build_ransac_grids(const float *tgt, const int32_t *n_tgt, int P, int Mmax, 
     const bool can = !want_hash && Mmax <= kDenseMaxPoints && S <= 32768 && grid_lds4_bytes(Mmax, S, budget) > 0;
     if (!can) {
         PCR_REQUIRE(!want_dense, PCR_ERR_ARG, "ransac: PCR_RANSAC_GRID=dense, but %d points per cloud do not fit LDS", Mmax);
-        return build_grids(tgt, n_tgt, P, Mmax, r, s, 4, out, 2.01, 3);
+        return build_grids(tgt, n_tgt, P, Mmax, r, s, kWsRansacGrid, out, 2.01, 3);
     }
     const int tab = (int)((budget - (size_t)Mmax * 16) & ~size_t(15));
-    int rc = build_grids_auto(tgt, n_tgt, P, Mmax, r, s, 4, out, tab, 3);
+    int rc = build_grids_auto(tgt, n_tgt, P, Mmax, r, s, kWsRansacGrid, out, tab, 3);
     if (rc != PCR_OK) return rc;
     return want_dense ? require_all_dense(out, P, s, "ransac") : PCR_OK;
 }
@@ -817,12 +817,14 @@ int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
     const size_t per = sizeof(int32_t) * (size_t)P * nm;
     a.nslots = (int)std::min<size_t>(32, ((size_t)256 << 20) / per);
     a.nslots = std::max(0, std::min(a.nslots, env_int("PCR_RANSAC_SLOTS", a.nslots)));
-    a.bestbuf = (int32_t *)workspace(21, per);
-    a.state = (RState *)workspace(22, sizeof(RState) * (size_t)P);
-    a.hdr = (RHeader *)workspace(25, 2 * sizeof(RHeader) + sizeof(int) * (size_t)P);
-    a.slots = (int32_t *)workspace(31, a.nslots > 0 ? per * a.nslots : 16);
+    a.bestbuf = (int32_t *)workspace(kWsRansacBest, per);
+    a.state = (RState *)workspace(kWsRansacState, sizeof(RState) * (size_t)P);
+    WsLayout lh;
+    lh.take(a.hdr, 2);
+    lh.take(a.ntask, P);
+    workspace_bind(kWsRansacHdr_FpfhLists, lh);  // a.hdr stays null when it fails
+    a.slots = (int32_t *)workspace(kWsRansacSlots, a.nslots > 0 ? per * a.nslots : 16);
     PCR_REQUIRE(a.bestbuf && a.state && a.hdr && a.slots, PCR_ERR_NOMEM, "ransac: %s", pcr_last_error());
-    a.ntask = (int *)(a.hdr + 2);
     a.prev_active = nullptr;
     a.grid = GridBatch{};
     a.grid.S = 1;
@@ -836,7 +838,7 @@ int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
             int rc = build_ransac_grids(tgt, n_tgt, P, Mmax, a.d, s, a.grid);
             if (rc != PCR_OK) return rc;
             if (Nmax > 0) {
-                rc = spatial_order(src, n_src, P, Nmax, a.grid.cell, s, 13, &a.order, &a.srcp, 36);
+                rc = spatial_order(src, n_src, P, Nmax, a.grid.cell, s, kWsRansacOrder, &a.order, &a.srcp, kWsRansacPerm);
                 if (rc != PCR_OK) return rc;
             }
         }
@@ -893,11 +895,11 @@ int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
         // max_iteration fits the first round), a multiple of 256
         a.hcap = a.max_iter > kRound0 ? (g ? std::max(span1, kRound0) : kRoundN)
                                       : std::max(256, (std::max(a.max_iter, 1) + 255) / 256 * 256);
-        a.hypT = (double *)workspace(23, sizeof(double) * 12 * (size_t)P * a.hcap);
-        a.hypbits = (unsigned long long *)workspace(24, sizeof(unsigned long long) * (size_t)P * (a.hcap / 64));
-        a.tasks = (int *)workspace(29, sizeof(int) * (size_t)P * a.hcap);
-        a.res = (TaskRes *)workspace(30, sizeof(TaskRes) * (size_t)P * a.hcap);
-        a.parts = split > 1 ? (TaskPart *)workspace(32, sizeof(TaskPart) * (size_t)split * P * a.hcap) : nullptr;
+        a.hypT = (double *)workspace(kWsRansacHypT, sizeof(double) * 12 * (size_t)P * a.hcap);
+        a.hypbits = (unsigned long long *)workspace(kWsRansacHypBits_FpfhGrid, sizeof(unsigned long long) * (size_t)P * (a.hcap / 64));
+        a.tasks = (int *)workspace(kWsRansacTasks, sizeof(int) * (size_t)P * a.hcap);
+        a.res = (TaskRes *)workspace(kWsRansacRes, sizeof(TaskRes) * (size_t)P * a.hcap);
+        a.parts = split > 1 ? (TaskPart *)workspace(kWsRansacParts, sizeof(TaskPart) * (size_t)split * P * a.hcap) : nullptr;
         return a.hypT && a.hypbits && a.tasks && a.res && (split == 1 || a.parts);
     };
     if (!alloc_slots(gated)) {

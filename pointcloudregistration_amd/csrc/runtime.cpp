@@ -36,7 +36,7 @@ struct Slot {
     bool dirty = false;  // workspace_dirty: the owner's last use did not complete
 };
 constexpr int kMaxDevices = 64;
-constexpr int kMaxSlots = 40;
+constexpr int kMaxSlots = kWsCount;  // one table entry per slot name (workspace.h)
 constexpr int kMaxCtx = 4;  // workspace contexts (pcr_set_workspace_context)
 std::mutex g_mu;
 Slot g_slots[kMaxDevices][kMaxCtx][kMaxSlots];
@@ -52,7 +52,7 @@ int g_conc = 1;
 std::vector<std::pair<int, void *>> g_retired;
 }  // namespace
 
-bool *workspace_dirty(int slot) {
+bool *workspace_dirty(WsSlot slot) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices || slot < 0 || slot >= kMaxSlots)
         return nullptr;
@@ -60,7 +60,7 @@ bool *workspace_dirty(int slot) {
     return &g_slots[dev][t_ctx][slot].dirty;
 }
 
-void *workspace(int slot, size_t bytes, bool *fresh) {
+void *workspace(WsSlot slot, size_t bytes, bool *fresh) {
     if (fresh) *fresh = false;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices || slot < 0 ||
@@ -84,6 +84,20 @@ void *workspace(int slot, size_t bytes, bool *fresh) {
     s.ptr = p;
     s.bytes = want;
     if (fresh) *fresh = true;
+    return p;
+}
+
+void *workspace_bind(WsSlot slot, const WsLayout &l, size_t slack, bool *fresh) {
+    if (fresh) *fresh = false;
+    if (!l.ok() || l.bytes() > SIZE_MAX - slack) {
+        set_error("workspace: the layout of slot %d overflows", (int)slot);
+        return nullptr;
+    }
+    void *p = workspace(slot, l.bytes() + slack, fresh);
+    if (p && !l.bind(p)) {
+        set_error("workspace: slot %d at %p is not aligned to %zu", (int)slot, p, l.alignment());
+        return nullptr;
+    }
     return p;
 }
 

@@ -162,16 +162,6 @@ __global__ void vd_emit(VArgs a, const int *outr, int total, const int *list, co
 }
 
 inline unsigned nbits(u64 x) { return x ? 64u - (unsigned)__builtin_clzll(x) : 0u; }
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Carve {
-    size_t used = 0;
-    template <class T> size_t take(size_t count) {
-        const size_t at = used;
-        used = align256(used + sizeof(T) * (count > 0 ? count : 1));
-        return at;
-    }
-};
 
 // Eigen::Vector3i key with Open3D's utility::hash_eigen (boost hash_combine
 // over the coefficients; std::hash<int> is the identity in libstdc++)
@@ -291,26 +281,18 @@ extern "C" int pcr_voxel_down_sample(const double *points, int32_t n, const int3
     for (int b = 0; b < nb; ++b) out_cloud_len[b] = 0;
     if (N == 0) return PCR_OK;
     hipStream_t st = as_stream(stream);
-    Carve c;
-    const size_t o_off = c.take<int>(nb + 1), o_bb = c.take<double>(6 * (size_t)nb),
-                 o_vmb = c.take<double>(3 * (size_t)nb), o_bad = c.take<int>(2),
-                 o_key = c.take<u64>(N), o_skey = c.take<u64>(N), o_iota = c.take<int>(N),
-                 o_v = c.take<int>(N), o_head = c.take<unsigned char>(N), o_start = c.take<int>(N + 1),
-                 o_mark = c.take<int>(N), o_list = c.take<int>(N), o_okey = c.take<u64>(N),
-                 o_outr = c.take<int>(N), o_cnt = c.take<int>(2);
-    char *ws = (char *)workspace(27, c.used);
-    PCR_REQUIRE(ws, PCR_ERR_NOMEM, "voxel_down_sample: %s", pcr_last_error());
     VArgs a;
+    u64 *skey, *okey;
+    int *v, *start, *mark, *list, *outr, *dcnt;
+    unsigned char *head;
+    WsLayout l(256);
+    l.take(a.off, nb + 1); l.take(a.bbox, 6 * (size_t)nb); l.take(a.vmb, 3 * (size_t)nb); l.take(a.bad, 2);
+    l.take(a.key, N); l.take(skey, N); l.take(a.iota, N); l.take(v, N);
+    l.take(head, N); l.take(start, N + 1); l.take(mark, N); l.take(list, N);
+    l.take(okey, N); l.take(outr, N); l.take(dcnt, 2);
+    PCR_REQUIRE(workspace_bind(kWsVoxel, l), PCR_ERR_NOMEM, "voxel_down_sample: %s", pcr_last_error());
     a.pts = points; a.nrm = normals; a.col = colors; a.n = N; a.nb = nb;
-    a.off = (int *)(ws + o_off); a.voxel = voxel_size;
-    a.bbox = (double *)(ws + o_bb); a.vmb = (const double *)(ws + o_vmb); a.bad = (int *)(ws + o_bad);
-    a.key = (u64 *)(ws + o_key); a.iota = (int *)(ws + o_iota);
-    u64 *skey = (u64 *)(ws + o_skey);
-    int *v = (int *)(ws + o_v);
-    unsigned char *head = (unsigned char *)(ws + o_head);
-    int *start = (int *)(ws + o_start), *mark = (int *)(ws + o_mark), *list = (int *)(ws + o_list);
-    u64 *okey = (u64 *)(ws + o_okey);
-    int *outr = (int *)(ws + o_outr), *dcnt = (int *)(ws + o_cnt);
+    a.voxel = voxel_size;
 
     PCR_HIP_CHECK(hipMemcpyAsync((void *)a.off, off.data(), sizeof(int) * (nb + 1), hipMemcpyHostToDevice, st));
     PCR_HIP_CHECK(hipMemsetAsync(a.bad, 0, sizeof(int), st));
@@ -363,7 +345,7 @@ extern "C" int pcr_voxel_down_sample(const double *points, int32_t n, const int3
     tb = std::max(tb, t1);
     PCR_HIP_CHECK(rocprim::select(nullptr, t1, mark, list, dcnt + 1, (size_t)N, NonNeg(), st));
     tb = std::max(tb, t1);
-    void *tmp = workspace(28, tb);
+    void *tmp = workspace(kWsVoxelTmp, tb);
     PCR_REQUIRE(tmp, PCR_ERR_NOMEM, "voxel_down_sample: %s", pcr_last_error());
     t1 = tb;
     PCR_HIP_CHECK(rocprim::radix_sort_pairs(tmp, t1, a.key, skey, a.iota, v, N, 0, kb, st));
