@@ -685,6 +685,58 @@ int pcr_ball_query(const float *xyz, const float *query, int32_t b, int32_t n, i
 int pcr_group_ppf(const float *xyz, const float *normals, int32_t b, int32_t n, float r2, int32_t k,
                   int32_t channels_first, float *feat, int32_t *idx, pcr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Similarity top-k matching: the correspondence stage of ROPNet's
+ * TFMRModule.forward (ROPNet/src/models/TFMR.py:226-257) -- bmm similarity, row
+ * maxima, the sort that keeps the most confident source rows, topk, the
+ * index_put mask, the normalisation and the bmm against the target points --
+ * without any (b,n1,m1) tensor.  Its outputs (src[sel], tgt_corr, the overlap
+ * scores at sel) are what pcr_procrustes_batch consumes.
+ *
+ * Inputs.  fx (b,n1,c), fy (b,m1,c) f32: the normalised, gathered features
+ *   (c = 5 x feat_dim = 960 in the reference); tgt (b,m1,3) f32.
+ * Similarity.  S[i][j] is the f32 fmaf chain over ch = 0 .. c-1 ascending from
+ *   +0: s = fmaf(x[i][ch], y[j][ch], s).  One accumulator of
+ *   v_mfma_f32_32x32x2_f32 carried through every k-step computes exactly that
+ *   (one rounding per product, subnormals kept), so there is no error bound
+ *   and no rescan, and a CPU restatement matches bit for bit.  No split-K.
+ * Top-k.  Per row the k largest by (S descending, j ascending); -0 equals +0
+ *   (and is reported as +0), so ties go to the lowest index.  val (b,n1,k)
+ *   f32 and idx (b,n1,k) i32, both in that order.
+ * Row selection.  The rows of a batch ordered by (val[.][0] descending, i
+ *   ascending); sel (b,n_keep) i32 holds the first n_keep.  The caller
+ *   computes n_keep = int(top_prob * n1).
+ * Weights and correspondences, per kept row, f32, every operation rounded:
+ *   sum = ((v0 + v1) + ...) in top-k order, den = sum + 1e-8f, w_t = v_t / den
+ *   (correctly rounded), tgt_corr[d] = ((w0 t0[d]) + w1 t1[d]) + ... with
+ *   t_t = tgt[idx_t].  Negative or zero sums are not special-cased: the
+ *   formulas are the reference's.
+ * Non-finite features: values unspecified; every index stays in range, sel
+ *   stays distinct, every kernel terminates.
+ * Limits.  1 <= k <= 8, k <= m1; n1, m1 in 1 .. 2^24; c in 1 .. 65536 (looped in
+ *   chunks of 32); 0 <= n_keep <= n1; b x ceil(n1 / 128) x ceil(m1 / 128) < 2^31.
+ *   Anything else returns PCR_ERR_ARG with its message before any device work.
+ *   b = 0 (and, for the selection, n_keep = 0) returns PCR_OK without a launch.
+ *
+ * pcr_tfmr_scratch_bytes: the bytes of the caller's scratch for these sizes
+ *   (8 b n1 (ceil(m1 / 128) k + 1), rounded up to 256: the target tiles' lists
+ *   and one key per row; nothing proportional to n1 m1), or -1 on bad sizes.
+ * pcr_similarity_topk: val and idx of every row.  scratch: that many bytes,
+ *   256-byte aligned, device memory; the call leaves the rows' selection keys
+ *   in it.
+ * pcr_tfmr_select: sel, w (b,n_keep,k), tgt_corr (b,n_keep,3) and idx_keep
+ *   (b,n_keep,k), the kept rows' idx.  val, idx and scratch are the ones a
+ *   pcr_similarity_topk call with the same b, n1, m1, k filled (on the same
+ *   stream, or ordered behind it): the selection reads the keys it left.
+ * Both are asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+int64_t pcr_tfmr_scratch_bytes(int32_t b, int32_t n1, int32_t m1, int32_t c, int32_t k);
+int pcr_similarity_topk(const float *fx, const float *fy, int32_t b, int32_t n1, int32_t m1, int32_t c,
+                        int32_t k, float *val, int32_t *idx, void *scratch, pcr_stream_t stream);
+int pcr_tfmr_select(const float *val, const int32_t *idx, const float *tgt, int32_t b, int32_t n1,
+                    int32_t m1, int32_t k, int32_t n_keep, int32_t *sel, float *w, float *tgt_corr,
+                    int32_t *idx_keep, const void *scratch, pcr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,15 +7,17 @@ reference's operator interfaces:
   nndistance     torch_nndistance.nnd / NNDFunction / torch_nndistance_aten
   grouping       fps / gather_points / ball_query / sample_and_group of ROPNet's
                  model_utils and NgeNet's process, and the fused PPF group
+  matching       the similarity top-k matching of ROPNet's TFMRModule.forward
+                 (similarity, row selection, weights and correspondences)
 """
 from ._lib import PcrError, load as load_library  # noqa: F401
 
-__all__ = ["PcrError", "load_library", "grouping"]
+__all__ = ["PcrError", "load_library", "grouping", "matching"]
 
 
 def __getattr__(name):
     # the op modules import torch; the package itself (ABI loader) does not
-    if name == "grouping":
+    if name in ("grouping", "matching"):
         import importlib
-        return importlib.import_module(".grouping", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
