@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "geom.h"
 #include "grid_dense.h"
+#include "lds_fit.h"
 
 namespace pcr {
 
@@ -440,10 +441,7 @@ inline int grid_slots(int Mmax, int slot_num) {
 
 // bytes of the float4 LDS copy of one pair's grid (0 if it does not fit)
 inline size_t grid_lds4_bytes(int mstride, int S, size_t budget) {
-    if (mstride > 65535 || S + 1 > 65536) return 0;
-    const size_t b = (size_t)mstride * 16 + (size_t)(S + 1) * 2;
-    const size_t a = (b + 15) & ~size_t(15);
-    return a <= budget ? a : 0;
+    return lds4_fit_bytes(mstride, S, budget);
 }
 
 // cooperative float4 copy of pair p's grid into LDS (all threads of the block

@@ -24,7 +24,10 @@
 #include "scan.h"
 #include "nng.h"
 #include "geom.h"
+#include "lds_fit.h"
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 namespace pcr {
 namespace {
@@ -220,8 +223,22 @@ __device__ __forceinline__ int xcd_slot(int L, int total) {
 // merge their (d, j) minima before the certification test; the minimum of
 // (d, j) pairs does not depend on the merge order, so every LPQ gives the same
 // answer.
+//
+// The one-lane form is bound by the latency of each wave's own chain (loads
+// and dependent instructions), not by issue: what a SIMD gets through scales
+// with the waves it holds.  It asks for kQueryWaves = 8 waves per SIMD: 64
+// VGPRs and 20 B of scratch per lane, where the compiler left alone takes 75
+// VGPRs and fits 6 waves, and 7 waves take 72 with no scratch.  C4 query, 256 /
+// 64 / 32 pairs: 0.456 / 0.134 / 0.083 ms at 6 waves, 0.421 / 0.128 / 0.082 at
+// 7, 0.414 / 0.123 / 0.071 at 8 (tools/build_variant.sh
+// NAME -DPCR_NNG_QUERY_WAVES=n builds the others).
+#ifndef PCR_NNG_QUERY_WAVES
+#define PCR_NNG_QUERY_WAVES 8
+#endif
+constexpr int kQueryWaves = PCR_NNG_QUERY_WAVES;
+
 template <int LPQ>
-__global__ __launch_bounds__(256) void nng_query(NgArgs a, int nchunk) {
+__global__ __launch_bounds__(256, LPQ == 1 ? kQueryWaves : 1) void nng_query(NgArgs a, int nchunk) {
     if (gated_off(a.gate)) return;
     constexpr int QPB = 256 / LPQ;
     const int w = xcd_slot(blockIdx.x, gridDim.x);
@@ -292,6 +309,137 @@ __global__ __launch_bounds__(256) void nng_query(NgArgs a, int nchunk) {
     }
 }
 
+// The batch form of the query, the candidate cloud's grid in LDS.  Not the
+// default: at C4 it measured 0.49 ms against nng_query<1>'s 0.45 (one
+// workgroup of 16 waves per CU is all that 147 KB of LDS allows, and with four
+// waves per SIMD the walk's own instruction latency takes the place of the L2
+// round trips).  PCR_NND_QUERY=lds selects it.  In
+// nng_query every lane chases start[h], start[h + 1] and pts[s..] through L2 (a
+// C4 launch walks 512 grids of ~160 KB, 82 MB against 4 MB of L2 per XCD), a
+// chain of ~26 dependent round trips per query.  Here one 1024-thread
+// workgroup owns one (direction, pair) -- or one of K contiguous shares of its
+// queries, so that a small batch still fills the chip; the K workgroups of a
+// cloud stage the same grid and never meet -- and copies the grid once: the
+// float4 points as they are, the S + 1 slot starts narrowed to u16 (lds_fit.h;
+// the layout of grid_to_lds4).  The walk is nng::ring_walk itself on an LDS
+// view and the fallback scan reads the LDS points, so every arithmetic step,
+// the certification and the tie rule are nng_query<1>'s, bit for bit.
+//
+// Queries go in the slot order of their own cloud's grid, in 64-query chunks
+// that a wave takes from an LDS counter (dense and sparse regions cost
+// different time); a wave loads its next chunk's queries before it walks the
+// current one.  A pair sent to the reference loop has no grid: its workgroups
+// stage nothing and run that loop from global memory, as nng_query does.
+constexpr int kLdsQueryThreads = 1024;
+
+__global__ __launch_bounds__(kLdsQueryThreads) void nng_query_lds(NgArgs a, int K) {
+    if (gated_off(a.gate)) return;
+    extern __shared__ __align__(16) char nng_dsm[];  // pts [nmax] float4, start16 [S + 1]
+    __shared__ int next_chunk;
+    // the K shares of one cloud take consecutive slots of one XCD's range
+    // (xcd_slot): its grid is fetched into one L2
+    const int w = xcd_slot(blockIdx.x, gridDim.x);
+    const int grp = w / K, part = w - grp * K;
+    const int dir = grp / a.B, b = grp - dir * a.B;
+    const int qs = dir, gs = 1 - dir;  // queries from set dir, candidates from the other set
+    const int nq = a.n[qs], m = a.n[gs];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const bool refl = ref_loop(a, b);
+    const size_t g = (size_t)gs * a.B + b;
+    float4 *lp = (float4 *)nng_dsm;
+    uint16_t *ls = (uint16_t *)(lp + a.nmax);
+    if (tid == 0) next_chunk = 0;
+    if (!refl) {
+        const float4 *gp = a.pts + g * a.nmax;
+#pragma unroll 4
+        for (int i = tid; i < m; i += kLdsQueryThreads) lp[i] = gp[i];
+        // two starts per lane: entries 2i and 2i + 1 as one 32-bit LDS word (the
+        // last entry, S, is even and goes alone)
+        const int *st = a.start + g * (a.S + 1);
+#pragma unroll 4
+        for (int i = tid; 2 * i <= a.S; i += kLdsQueryThreads) {
+            const unsigned lo = (unsigned)st[2 * i];
+            if (2 * i < a.S) ((uint32_t *)ls)[i] = lo | ((unsigned)st[2 * i + 1] << 16);
+            else ls[2 * i] = (uint16_t)lo;
+        }
+    }
+    __syncthreads();
+    const nng::ViewLds v{refl ? 1.f : a.cell[g], a.S, {(const PCR_NNG_LDS uint16_t *)ls},
+                         {(const PCR_NNG_LDS nng::LdsPts::vec4 *)lp}};
+    const float *C = a.xyz[gs] + (size_t)b * m * 3;
+    const float4 *qpts = a.pts + ((size_t)qs * a.B + b) * a.nmax;
+    const float *qxyz = a.xyz[qs] + (size_t)b * nq * 3;
+    // this workgroup's share of the 64-query chunks
+    const int nchunk = (nq + 63) >> 6;
+    const int c_lo = (int)((long long)nchunk * part / K), c_hi = (int)((long long)nchunk * (part + 1) / K);
+    auto take_chunk = [&]() {
+        int c = 0;
+        if (lane == 0) c = atomicAdd(&next_chunk, 1);
+        return __shfl(c, 0, 64) + c_lo;
+    };
+    // the query of position k: (x, y, z, index bits) -- a grid's cell-sorted copy,
+    // or for the reference loop the cloud in index order
+    auto load_query = [&](int c) {
+        const int k = (c << 6) + lane;
+        if (c >= c_hi || k >= nq) return make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+        if (refl) return make_float4(qxyz[3 * k], qxyz[3 * k + 1], qxyz[3 * k + 2], __int_as_float(k));
+        return qpts[k];
+    };
+    int c = take_chunk();
+    float4 q = load_query(c);
+    while (c < c_hi) {
+        const int cn = take_chunk();
+        const float4 qn = load_query(cn);
+        const int qi = __float_as_int(q.w);
+        if (qi >= 0) {
+            float best = __builtin_inff();
+            int bj = 0x7fffffff;
+            if (refl) {
+                // the reference loop: seed with candidate 0, strict < (my_lib.cpp:11-20)
+                best = d2f(C[0], C[1], C[2], q.x, q.y, q.z);
+                bj = 0;
+                for (int j = 1; j < m; ++j) {
+                    const float d = d2f(C[3 * j], C[3 * j + 1], C[3 * j + 2], q.x, q.y, q.z);
+                    if (d < best) { best = d; bj = j; }
+                }
+            } else if (!nng::ring_walk<1>(v, q.x, q.y, q.z, 0, kMaxRing, best, bj)) {
+                // not certified within kMaxRing rings: every candidate, from LDS
+#pragma unroll 4
+                for (int s = 0; s < m; ++s) {
+                    const float4 p = v.pts[s];
+                    const float d = d2f(p.x, p.y, p.z, q.x, q.y, q.z);
+                    const int j = __float_as_int(p.w);
+                    if (d < best || (d == best && j < bj)) { best = d; bj = j; }
+                }
+            }
+            a.dist[dir][(size_t)b * nq + qi] = best;
+            a.idx[dir][(size_t)b * nq + qi] = bj;
+        }
+        c = cn;
+        q = qn;
+    }
+}
+
+// how a call's queries are served: PCR_NND_QUERY (test hook, read per call) =
+// auto (default) or l2: nng_query; lds: nng_query_lds, or an error where the
+// grid does not fit -- a forced call that returns was served by that kernel
+enum class QueryMode { kAuto, kL2, kLds };
+
+// the dynamic LDS a workgroup of kernel fn may have: the device's LDS per
+// workgroup less fn's static LDS (both asked of the runtime); raises fn's limit to it
+struct LdsLimit { hipError_t err; size_t dyn; };
+LdsLimit lds_limit(const void *fn) {
+    int dev = 0, per_wg = 0;
+    hipFuncAttributes fa;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&per_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    if (e == hipSuccess) e = hipFuncGetAttributes(&fa, fn);
+    if (e != hipSuccess) return LdsLimit{e, 0};
+    const size_t dyn = (size_t)per_wg > fa.sharedSizeBytes ? (size_t)per_wg - fa.sharedSizeBytes : 0;
+    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    return LdsLimit{e, dyn};
+}
+
 }  // namespace
 
 int nnd_forward_grid(const float *xyz1, const float *xyz2, int b, int n, int m, float *dist1,
@@ -321,6 +469,39 @@ int nnd_forward_grid_xf(const float *xyz1, const float *src, const double *T, co
     a.cf = 0.6f;  // 0.4 / 0.5 / 0.6 / 0.8 / 1.0 x cbrt(V / n) measured
     const bool lds_build = S <= kLdsSlots;
     PCR_REQUIRE(lds_build || !src, PCR_ERR_ARG, "nnd_forward (grid): fused transform needs the LDS build");
+    // lanes per query: one thread per query once the launch fills the chip
+    // (PCR_NND_LPQ = 1|2|4|8|16 overrides)
+    const long long nq = (long long)b * (n + m);
+    int lpq = nq >= (1LL << 18) ? 1 : nq >= (1LL << 16) ? 4 : 8;
+    if (const char *e = getenv("PCR_NND_LPQ")) {
+        const int v = atoi(e);
+        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) lpq = v;
+    }
+    // The query kernel: nng_query.  The LDS walk was built for the batches in
+    // the one-lane-per-query regime and measured slower there at 256, 64 and 32
+    // pairs, so no size selects it: it runs only when
+    // PCR_NND_QUERY=lds asks for it, and then the grid must have been built by
+    // nng_bbox_build and its copy must fit the LDS a workgroup may have beside
+    // the kernel's static LDS (both asked of the runtime) -- or the call fails.
+    QueryMode mode = QueryMode::kAuto;
+    if (const char *e = getenv("PCR_NND_QUERY")) {
+        mode = !strcmp(e, "l2") ? QueryMode::kL2 : !strcmp(e, "lds") ? QueryMode::kLds : QueryMode::kAuto;
+        PCR_REQUIRE(mode != QueryMode::kAuto || !strcmp(e, "auto"), PCR_ERR_ARG,
+                    "nnd_forward (grid): PCR_NND_QUERY=%s (auto, l2 or lds)", e);
+    }
+    size_t lds_bytes = 0;
+    if (mode == QueryMode::kLds) {
+        if (lds_build) {
+            // asked once, and the attribute set once: the first forced call is an
+            // eager one (a test hook; never inside a stream capture)
+            static const LdsLimit lim = lds_limit((const void *)nng_query_lds);
+            PCR_HIP_CHECK(lim.err);
+            lds_bytes = lds4_fit_bytes(a.nmax, S, lim.dyn);
+        }
+        PCR_REQUIRE(lds_bytes > 0, PCR_ERR_ARG,
+                    "nnd_forward (grid): PCR_NND_QUERY=lds, but a grid of %d points and %d slots does not fit LDS",
+                    a.nmax, S);
+    }
     if (!lds_build) PCR_HIP_CHECK(hipMemsetAsync(a.hcnt, 0, sizeof(int) * hc, s));
     if (lds_build) {
         // the attribute is set once, outside any stream capture (the NDP level
@@ -344,13 +525,13 @@ int nnd_forward_grid_xf(const float *xyz1, const float *src, const double *T, co
         PCR_LAUNCH_CHECK();
     }
     prof_begin(s, kProfNndGrid);
-    // lanes per query: one thread per query once the launch fills the chip
-    // (PCR_NND_LPQ = 1|2|4|8|16 overrides)
-    const long long nq = (long long)b * (n + m);
-    int lpq = nq >= (1LL << 18) ? 1 : nq >= (1LL << 16) ? 4 : 8;
-    if (const char *e = getenv("PCR_NND_LPQ")) {
-        const int v = atoi(e);
-        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) lpq = v;
+    if (lds_bytes > 0) {
+        // K workgroups per (direction, pair): a 32- or 64-pair shard also fills the chip
+        const int K = std::min(std::max(kCUs / (2 * b), 1), 8);
+        hipLaunchKernelGGL(nng_query_lds, dim3(2 * b * K), dim3(kLdsQueryThreads), lds_bytes, s, a, K);
+        PCR_LAUNCH_CHECK();
+        prof_end(s, kProfNndGrid);
+        return PCR_OK;
     }
     const int nchunk = (a.nmax + 256 / lpq - 1) / (256 / lpq);
     const dim3 qg(2 * b * nchunk), qb(256);

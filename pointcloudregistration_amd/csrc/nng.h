@@ -52,6 +52,30 @@ struct View {
     const float4 *pts;
 };
 
+// the same view of a copy staged in LDS (nng_query_lds): float4 points and the
+// slot starts narrowed to u16 (a cloud of at most 65535 points, lds_fit.h).
+// The members carry the LDS address space, so ring_walk's v.start[h] and
+// v.pts[s] compile to ds_read_u16 / ds_read_b128 and not to flat loads.
+#define PCR_NNG_LDS __attribute__((address_space(3)))
+struct LdsPts {
+    typedef float vec4 __attribute__((ext_vector_type(4)));
+    const PCR_NNG_LDS vec4 *p;
+    __device__ __forceinline__ float4 operator[](int i) const {
+        const vec4 v = p[i];
+        return make_float4(v.x, v.y, v.z, v.w);
+    }
+};
+struct LdsStarts {
+    const PCR_NNG_LDS uint16_t *p;
+    __device__ __forceinline__ int operator[](unsigned i) const { return (int)p[i]; }
+};
+struct ViewLds {
+    float cell;
+    int S;
+    LdsStarts start;
+    LdsPts pts;
+};
+
 // Chebyshev rings k = 0..kmax around q's cell; the LPQ lanes of a query split
 // each ring's (dx, dy) columns and merge their minima before every
 // certification test.  After ring k every unvisited point is at least g (the
