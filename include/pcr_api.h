@@ -643,7 +643,7 @@ int pcr_ndp_chamfer_step(const pcr_ndp_chamfer *c, pcr_stream_t stream);
  * radius, (float)((double)radius * radius) for the reference's `radius ** 2`;
  * j is a neighbour iff !(d2 > r2), so a distance equal to the radius is
  * inside.  Ties go to the lowest index.  Non-finite coordinates give
- * unspecified results.  All buffers are device memory; all three entries are
+ * unspecified results.  All buffers are device memory; all entries are
  * asynchronous on `stream`; n >= 1 and n < 2^31 / 3.
  *
  * pcr_fps: farthest-point sampling.  xyz (b,n,3) f32, start (b) i32 with
@@ -677,6 +677,34 @@ int pcr_ndp_chamfer_step(const pcr_ndp_chamfer *c, pcr_stream_t stream);
  *   with channels_first = 0 and (b,C,k,n) -- the Conv2d layout of TFMR.py:71 --
  *   with channels_first = 1.  Channels 0-5 are exact; 6-9 up to the device's
  *   atan2f / sqrtf.
+ *
+ * pcr_knn_graph: the k-nearest-neighbour graph of get_graph_features
+ *   (ngenet/models/information_interactive.py:7-23, called twice by
+ *   GCN.forward, :107-130) without a (b,n,n) array or a sort.  xyz (b,n,3) f32,
+ *   1 <= k <= 63, kk = min(k, n - 1).  For every point i, all n points of its
+ *   cloud, i included, are ordered by the pair (d2(x_i, x_j), j) ascending;
+ *   row i of idx (b,n,kk) i32 holds ranks 1 .. kk of that order.  Rank 0 is
+ *   dropped, as the reference drops column 0 of its topk: without coincident
+ *   points it is i itself; with coincident points it is the lowest-index point
+ *   at distance 0 and the row may then contain i (the reference's choice there
+ *   is an unspecified topk tie).  d2 (b,n,kk) f32 or NULL receives the
+ *   distances of those ranks, ascending.  Exact and deterministic: every key
+ *   of a row is distinct, so no chunking or scheduling can change the result.
+ *   kk = 0 (n = 1) or b = 0 returns PCR_OK with no launch and needs no
+ *   pointers.  No scratch.
+ *
+ * pcr_edge_features: the gather of get_graph_features.  feats (b,n,c) f32,
+ *   c >= 1; idx (b,n,kk) i32 with 0 <= idx < n (a PRECONDITION like pcr_fps's
+ *   start: the kernel clamps the values into [0, n) so that it never reads
+ *   outside the cloud), 0 <= kk <= 63.  With channels_first = 0, out is
+ *   (b,n,kk,2c): out[..., :c] = f_i and out[..., c:] = f_j - f_i, one f32
+ *   subtraction, j = idx[b][i][rank].  With channels_first = 1 the same values
+ *   as (b,2c,n,kk), what GCN feeds its Conv2d after
+ *   .permute(0, 3, 1, 2).contiguous().  Every value is exact; element offsets
+ *   are 64-bit.  kk = 0 or b = 0 returns PCR_OK with no launch.
+ *
+ * Both validate before any device work: a bad argument sets pcr_last_error
+ *   ("k=64 outside 1..63", "null pointer", ...) and returns PCR_ERR_ARG.
  * ------------------------------------------------------------------------- */
 int pcr_fps(const float *xyz, const int32_t *start, int32_t b, int32_t n, int32_t m, int32_t *idx,
             pcr_stream_t stream);
@@ -684,6 +712,10 @@ int pcr_ball_query(const float *xyz, const float *query, int32_t b, int32_t n, i
                    int32_t k, int32_t *idx, int32_t *count, pcr_stream_t stream);
 int pcr_group_ppf(const float *xyz, const float *normals, int32_t b, int32_t n, float r2, int32_t k,
                   int32_t channels_first, float *feat, int32_t *idx, pcr_stream_t stream);
+int pcr_knn_graph(const float *xyz, int32_t b, int32_t n, int32_t k, int32_t *idx, float *d2,
+                  pcr_stream_t stream);
+int pcr_edge_features(const float *feats, const int32_t *idx, int32_t b, int32_t n, int32_t c,
+                      int32_t kk, int32_t channels_first, float *out, pcr_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Similarity top-k matching: the correspondence stage of ROPNet's

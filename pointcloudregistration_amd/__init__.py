@@ -6,7 +6,9 @@ reference's operator interfaces:
 
   nndistance     torch_nndistance.nnd / NNDFunction / torch_nndistance_aten
   grouping       fps / gather_points / ball_query / sample_and_group of ROPNet's
-                 model_utils and NgeNet's process, and the fused PPF group
+                 model_utils and NgeNet's process, the fused PPF group, and the
+                 k-NN graph and edge features (get_graph_features) of
+                 NgeNet's GCN
   matching       the similarity top-k matching of ROPNet's TFMRModule.forward
                  (similarity, row selection, weights and correspondences)
 """

@@ -102,6 +102,8 @@ SIGNATURES = {
     "pcr_fps": [_p, _p, _i32, _i32, _i32, _p, _p],
     "pcr_ball_query": [_p, _p, _i32, _i32, _i32, _f32, _i32, _p, _p, _p],
     "pcr_group_ppf": [_p, _p, _i32, _i32, _f32, _i32, _i32, _p, _p, _p],
+    "pcr_knn_graph": [_p, _i32, _i32, _i32, _p, _p, _p],
+    "pcr_edge_features": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p],
     "pcr_similarity_topk": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
     "pcr_tfmr_select": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p],
 }

@@ -1,6 +1,7 @@
 """Point-set sampling and grouping on the GPU: drop-ins for the reference's
 ``fps`` / ``gather_points`` / ``ball_query`` / ``sample_and_group`` and the fused
-point-pair-feature group behind ``LocalFeatue`` and ``PPF``.
+point-pair-feature group behind ``LocalFeatue`` and ``PPF``, and for the k-NN
+graph and edge features (``get_graph_features``) behind NgeNet's ``GCN``.
 
 Reference surface:
   * ``ROPNet/src/models/model_utils.py:6-102``, consumed by
@@ -8,14 +9,24 @@ Reference surface:
   * ``c2p-net/ngenet/utils/process.py:57-115``, consumed by ``PPF.forward``
     (``ngenet/models/information_interactive.py:48-84``, ``ppf_k: 64``, radius
     ``0.025 * 32``);
+  * ``c2p-net/ngenet/models/information_interactive.py:7-23``
+    (``get_graph_features``), consumed twice per cloud by ``GCN.forward``
+    (``:107-130``, ``dgcnn_k: 10``, ``gnn_feats_dim: 256``);
   * ``dip/preprocess_lrf.py:97`` samples with ``torch_cluster.fps``.
 
 The reference forms a ``(B, N, N)`` f32 distance matrix and a ``(B, N, N)``
 int64 index tensor that it sorts; ``fps`` is a Python loop of ``M`` iterations.
 Here every call goes through libpcr.so (``pcr_fps``, ``pcr_ball_query``,
-``pcr_group_ppf``; contract in ``include/pcr_api.h``) on torch's current
-stream: squared distances in the direct form ``(dx*dx + dy*dy) + dz*dz``, a
-point at exactly the radius is inside, ties go to the lowest index.
+``pcr_group_ppf``, ``pcr_knn_graph``, ``pcr_edge_features``; contract in
+``include/pcr_api.h``) on torch's current stream: squared distances in the
+direct form ``(dx*dx + dy*dy) + dz*dz``, a point at exactly the radius is
+inside, ties go to the lowest index.
+
+``knn_graph`` orders a point's cloud by ``(d2, index)`` and drops rank 0 as the
+reference drops column 0 of its ``topk``; the reference breaks exact ties
+arbitrarily and ranks by the expanded form, so it is the neighbour *set* (all
+that ``GCN``'s max over the k axis sees) that equals the reference's, not
+always the order.  ``graph_features`` is the gather ``[f_i, f_j - f_i]``, exact.
 
 Like ``nndistance``, the module raises on CPU tensors (there is no fallback).
 The ops are forward-only: an input that requires grad while grad mode is on
@@ -27,7 +38,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["fps", "gather_points", "ball_query", "sample_and_group", "local_ppf_features"]
+__all__ = ["fps", "gather_points", "ball_query", "sample_and_group", "local_ppf_features",
+           "knn_graph", "graph_features"]
 
 
 def _cloud(name, t, last=3):
@@ -36,8 +48,8 @@ def _cloud(name, t, last=3):
     if not t.is_cuda:
         raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) "
                          "library and this module has no CPU path")
-    if t.dim() != 3 or t.shape[2] != last:
-        raise ValueError(f"{name} must be (B, N, {last}), got {tuple(t.shape)}")
+    if t.dim() != 3 or (last is not None and t.shape[2] != last) or t.shape[2] < 1:
+        raise ValueError(f"{name} must be (B, N, {last or 'C'}), got {tuple(t.shape)}")
     if t.dtype != torch.float32:
         raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
     if t.requires_grad and torch.is_grad_enabled():
@@ -168,3 +180,78 @@ def local_ppf_features(xyz, normals, radius, K, channels_first=True, return_inds
     if return_inds:
         return feat, idx.long()
     return feat
+
+
+_KNN_MAX_K = 63   # pcr_knn_graph: k + 1 keys fit one wave
+
+
+def _knn(coords, k, want_dists):
+    coords = _cloud("coords", coords)
+    B, N, _ = coords.shape
+    k = int(k)
+    if not 1 <= k <= _KNN_MAX_K:
+        raise ValueError(f"k={k} outside 1..{_KNN_MAX_K}")
+    if N < 1:
+        raise ValueError(f"knn_graph needs N >= 1, got N={N}")
+    kk = min(k, N - 1)
+    idx = torch.empty(B, N, kk, dtype=torch.int32, device=coords.device)
+    d2 = torch.empty(B, N, kk, dtype=torch.float32, device=coords.device) if want_dists else None
+    if B and kk:
+        with torch.cuda.device(coords.device):
+            _lib.call("pcr_knn_graph", _lib.ptr(coords), B, N, k, _lib.ptr(idx), _lib.ptr(d2),
+                      _lib.stream_handle(coords.device))
+    return idx, d2
+
+
+def knn_graph(coords, k, return_dists=False):
+    """``(B, N, min(k, N - 1))`` int64: per point the indices of its k nearest
+    other points, nearest first (``get_graph_features``' ``inds``,
+    information_interactive.py:16-19).  All N points, the point itself included,
+    are ranked by ``(d2, index)`` and rank 0 is dropped, as the reference drops
+    column 0: that is the point itself unless a lower-index point coincides with
+    it.  ``1 <= k <= 63``.  With ``return_dists`` also the f32 squared distances,
+    ascending."""
+    idx, d2 = _knn(coords, k, return_dists)
+    if return_dists:
+        return idx.long(), d2
+    return idx.long()
+
+
+def graph_features(feats, coords=None, k=10, inds=None, channels_first=False, return_inds=False):
+    """``get_graph_features(feats, coords, k)`` (information_interactive.py:7-23):
+    ``(B, N, kk, 2C)`` with ``[..., :C] = f_i`` and ``[..., C:] = f_j - f_i`` over
+    the ``kk = min(k, N - 1)`` nearest neighbours j of i; ``channels_first`` gives
+    the same values as ``(B, 2C, N, kk)``, the layout ``GCN`` hands its Conv2d.
+
+    Exactly one of ``coords (B, N, 3)`` and ``inds (B, N, kk)`` (integers in
+    ``[0, N)``, e.g. from ``knn_graph``) is given: ``inds`` lets ``GCN.forward``
+    build the graph once for its two calls.  With ``return_inds`` also the
+    ``(B, N, kk)`` int64 indices."""
+    feats = _cloud("feats", feats, last=None)
+    B, N, C = feats.shape
+    if (coords is None) == (inds is None):
+        raise ValueError("graph_features needs exactly one of coords and inds")
+    if coords is not None:
+        if not isinstance(coords, torch.Tensor) or coords.dim() != 3 or \
+                tuple(coords.shape[:2]) != (B, N) or coords.device != feats.device:
+            raise ValueError("coords must match feats in batch size, point count and device")
+        idx, _ = _knn(coords, k, False)
+    else:
+        if not isinstance(inds, torch.Tensor) or inds.dtype.is_floating_point or \
+                inds.dtype == torch.bool:
+            raise ValueError("inds must be an integer tensor")
+        if inds.dim() != 3 or tuple(inds.shape[:2]) != (B, N) or inds.device != feats.device:
+            raise ValueError(f"inds must be ({B}, {N}, kk) on feats' device, got {tuple(inds.shape)}")
+        if inds.shape[2] > _KNN_MAX_K:
+            raise ValueError(f"inds has {inds.shape[2]} columns, outside 0..{_KNN_MAX_K}")
+        idx = inds.to(torch.int32).contiguous()
+    kk = idx.shape[2]
+    shape = (B, 2 * C, N, kk) if channels_first else (B, N, kk, 2 * C)
+    out = torch.empty(shape, dtype=torch.float32, device=feats.device)
+    if B and kk:
+        with torch.cuda.device(feats.device):
+            _lib.call("pcr_edge_features", _lib.ptr(feats), _lib.ptr(idx), B, N, C, kk,
+                      1 if channels_first else 0, _lib.ptr(out), _lib.stream_handle(feats.device))
+    if return_inds:
+        return out, idx.long()
+    return out

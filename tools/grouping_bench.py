@@ -6,6 +6,15 @@ Shapes: fps at b=2, n=2048, m=512; ball_query and the fused point-pair group at
 b=2, n=2048, K=64, r=0.3 (ROPNet's LocalFeatue), and at K=64, r=0.8 on the same
 cloud scaled by 0.8 / 0.3 (NgeNet's PPF: ppf_k 64, radius 0.025 * 32).
 
+Also the k-NN graph and edge features of NgeNet's GCN (knn_graph,
+graph_features: dgcnn_k 10, gnn_feats_dim 256) at b=1, n in {512, 2048, 8192}
+and b=8, n=2048, beside the reference's tensor program restated from torch ops:
+the expanded-form (B,N,N) matrix, topk(k + 1, sorted), the gather, the repeat
+and the cat.  Only the neighbour sets and the feature bytes of rows whose order
+agrees are compared there (the reference ranks by the expanded form).  For
+graph_features the achieved bandwidth over its algorithmic bytes
+(B*N*kk*2C*4 written + B*N*C*4 read) is reported beside the time.
+
 The torch side is this project's own wording of the contract the way a tensor
 program has to do it: the (B,N,N) direct-form distance matrix, a (B,N,N) int64
 index tensor that is sorted, and the element-wise ops of the point-pair
@@ -77,6 +86,33 @@ def t_group_ppf(xyz, normals, radius, K):
     ppf = torch.stack([t_angle(ni, g), t_angle(nj, g), t_angle(ni, nj), torch.norm(g, dim=-1)], dim=-1)
     feat = torch.cat([xyz[:, :, None, :].expand(-1, -1, K, -1), g, ppf], dim=-1)
     return feat.permute(0, 3, 2, 1).contiguous(), inds
+
+
+def t_square_dists(a, b):
+    # the expanded form |a|^2 + |b|^2 - 2 a.b, as the reference's tensor program forms it
+    # (the same ops: two squared norms, one matmul, the clamp at 1e-8)
+    d = (a * a).sum(-1)[:, :, None] + (b * b).sum(-1)[:, None, :]
+    d -= 2 * torch.matmul(a, b.transpose(1, 2))
+    return d.clamp_(min=1e-8)
+
+
+def t_knn(coords, k):
+    n = coords.shape[1]
+    inds = torch.topk(t_square_dists(coords, coords), min(n, k + 1), dim=-1, largest=False, sorted=True)[1]
+    return inds[:, :, 1:]
+
+
+def t_edge_features(feats, inds, channels_first):
+    B = feats.shape[0]
+    rows = torch.arange(B, device=feats.device).view(B, 1, 1)
+    fj = feats[rows, inds]
+    fi = feats.unsqueeze(2).repeat(1, 1, inds.shape[2], 1)
+    out = torch.cat([fi, fj - fi], dim=-1)
+    return out.permute(0, 3, 1, 2).contiguous() if channels_first else out
+
+
+def t_graph_features(feats, coords, k, channels_first):
+    return t_edge_features(feats, t_knn(coords, k), channels_first)
 
 
 # ------------------------------------------------------------------- measurement
@@ -155,6 +191,40 @@ def main():
         add("local_ppf_features channels_last", s,
             lambda: grouping.local_ppf_features(x, nrm, r, K, channels_first=False),
             lambda: t_group_ppf(x, nrm, r, K)[0], args.reps, scratch=4 * B * N * K)
+    # the k-NN graph and edge features of NgeNet's GCN
+    C, k = 256, 10
+    for B, N in ((1, 512), (1, 2048), (1, 8192), (8, 2048)):
+        gen = torch.Generator().manual_seed(N + B)
+        x = (torch.rand(B, N, 3, generator=gen) * 2 - 1).cuda()
+        f = torch.randn(B, N, C, generator=gen).cuda()
+        inds, tinds = grouping.knn_graph(x, k), t_knn(x, k)
+        same_set = (inds.sort(-1)[0] == tinds.sort(-1)[0]).all(-1)
+        same_row = (inds == tinds).all(-1)
+        for cf in (False, True):
+            assert torch.equal(grouping.graph_features(f, inds=inds, channels_first=cf),
+                               t_edge_features(f, inds, cf)), "graph_features differs"
+        print(json.dumps({"check": f"knn b={B} n={N}", "rows": B * N,
+                          "rows_with_other_set": int((~same_set).sum()),
+                          "rows_with_other_order": int((~same_row).sum())}))
+        s = f"b={B} n={N} C={C} k={k}"
+        kk = min(k, N - 1)
+        algo_bytes = 4 * B * N * kk * 2 * C + 4 * B * N * C
+        add("knn_graph", s, lambda: grouping.knn_graph(x, k), lambda: t_knn(x, k), args.reps)
+        for cf in (False, True):
+            name = "channels_first" if cf else "channels_last"
+            add(f"edge features ({name}, inds given)", s,
+                lambda: grouping.graph_features(f, inds=inds, channels_first=cf),
+                lambda: t_edge_features(f, inds, cf), args.reps)
+            rows[-1]["algorithmic_bytes"] = algo_bytes
+            rows[-1]["library_bytes_per_s"] = algo_bytes / (rows[-1]["library"]["median_ms"] * 1e-3)
+            add(f"graph_features ({name}, from coords)", s,
+                lambda: grouping.graph_features(f, coords=x, k=k, channels_first=cf),
+                lambda: t_graph_features(f, x, k, cf), args.reps)
+            rows[-1]["algorithmic_bytes"] = algo_bytes
+            rows[-1]["library_bytes_per_s"] = algo_bytes / (rows[-1]["library"]["median_ms"] * 1e-3)
+            print(json.dumps({"op": rows[-1]["op"], "setting": s, "algorithmic_bytes": algo_bytes,
+                              "edge_only_bytes_per_s": rows[-2]["library_bytes_per_s"],
+                              "with_knn_bytes_per_s": rows[-1]["library_bytes_per_s"]}), flush=True)
     summary = {"device": torch.cuda.get_device_name(0), "rows": rows}
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
