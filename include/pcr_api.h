@@ -352,6 +352,10 @@ int pcr_legacy_choice_batch(uint32_t *key, int32_t *pos, const int32_t *pop, int
  * contiguously; w_nr/b_nr NULL for levels without the nonrigidity branch.
  * levels is a HOST array of n_levels (<= 16) entries.  x_levels (n_levels,N,3)
  * and nonrigidity (n_levels,N) are optional per-level outputs (data[i]).
+ * A point's result does not depend on its position in the cloud.  NaN
+ * propagates as in the reference: a point a level made NaN (a rotation branch
+ * that is exactly 0 divides 0 by 0) is NaN in every later level's points and
+ * nonrigidity (the ReLU keeps NaN, as torch's does).
  * ------------------------------------------------------------------------- */
 typedef struct pcr_ndp_level {
     const float *w_in, *b_in;   /* (W,6), (W) */
@@ -500,6 +504,13 @@ int pcr_compute_fpfh(const float *xyz, const double *normals, int32_t P, int32_t
  * pcr_adam_masked: torch.optim.Adam's update for n_tensors parameter tensors
  *   (a DEVICE table of pcr_adam_tensor), skipped when state[5] == 0; bias
  *   corrections from state[3] (steps taken, incremented by pcr_ndp_control).
+ *   The rule runs first: it increments state[3] *before* Adam reads it, so the
+ *   first applied step uses t = 1; state[3] must be >= 1 whenever state[5] is
+ *   set (t = 0 divides by 1 - beta1^0 = 0).  The launch is masked by state[5]
+ *   alone, not by pcr_set_gate: a gated level does not step because the rule
+ *   that cleared state[0] also cleared state[5].  Each tensor's result does not
+ *   depend on the other entries of the table; n_tensors <= 65535
+ *   (PCR_ERR_ARG above), and n_tensors = 0 or max_numel = 0 launch nothing.
  * ------------------------------------------------------------------------- */
 typedef struct pcr_adam_tensor {
     float *param;
@@ -518,7 +529,8 @@ int pcr_adam_masked(const pcr_adam_tensor *tensors, int32_t n_tensors, int32_t m
  *   `break`s out of the level).  While a gate is set on the calling thread
  *   (gate = the level's state, a device pointer), every kernel that
  *   pcr_nnd_forward / pcr_nnd_backward / pcr_ndp_train_forward /
- *   pcr_ndp_train_backward / pcr_ndp_chamfer_glue launch reads gate[0] at entry
+ *   pcr_ndp_train_backward / pcr_ndp_chamfer_glue / pcr_ndp_chamfer_step /
+ *   pcr_ndp_chamfer_loss launch reads gate[0] at entry
  *   and returns at once when it is 0 -- so the replays of a captured level graph
  *   left after the rule fired cost only their launches.  pcr_set_gate(NULL)
  *   restores ungated launches.  Thread-local; captured launches keep the pointer
@@ -573,7 +585,11 @@ int64_t pcr_ndp_train_partial_floats(int32_t N, int32_t width, int32_t depth, in
  *   is given), d' = d where d < trunc else 0; gd1 = 1/K and gd2 = 1/M where not
  *   truncated, else 0 (the dist gradients for pcr_nnd_backward; gd1 / gd2 may be
  *   null);
- *   log[min(*ctr, log_last)] = loss; ++*ctr (device int64). */
+ *   log[min(*ctr, log_last)] = loss; ++*ctr (device int64).
+ *   NaN in d1 / d2 stays (it is not >= trunc, its seed is 1/K), s == 1 counts
+ *   exactly -100, s > 1 gives NaN.  K = 0 or M = 0 launches and gives NaN
+ *   (0 / 0, as torch's mean of an empty tensor); pcr_ndp_chamfer_loss refuses
+ *   them (PCR_ERR_ARG, nothing written). */
 int pcr_ndp_chamfer_glue(const float *d1, int32_t K, const float *d2, int32_t M,
                          const float *s, int32_t N, double w_reg, double trunc,
                          float *gd1, float *gd2, float *loss, float *log, int64_t *ctr,

@@ -49,6 +49,10 @@ struct NdpArgs {
     NdpLevelDev lv[kMaxLevels];
 };
 
+// torch's ReLU: NaN stays NaN (fmaxf(NaN, 0) is 0, which gave a point that an
+// earlier level had made NaN a finite nonrigidity where the reference has NaN)
+__device__ __forceinline__ float relu(float v) { return v < 0.0f ? 0.0f : v; }
+
 template <int NT>
 __global__ __launch_bounds__(64 * NT) void ndp_warp_kernel(NdpArgs a) {
     constexpr int W = 32 * NT;
@@ -79,7 +83,7 @@ __global__ __launch_bounds__(64 * NT) void ndp_warp_kernel(NdpArgs a) {
             for (int s = 0; s < 3; ++s) H = __builtin_amdgcn_mfma_f32_32x32x2f32(wr[2 * s + h], pe[s], H, 0, 0, 0);
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) H[r] = fmaxf(H[r], 0.0f);
+        for (int r = 0; r < 16; ++r) H[r] = relu(H[r]);
         for (int hl = 0; hl + 1 < a.depth; ++hl) {
             publish(X[w], l, H);
             __syncthreads();
@@ -91,7 +95,7 @@ __global__ __launch_bounds__(64 * NT) void ndp_warp_kernel(NdpArgs a) {
             Hn = chain<NT>(X, l, [&](int it, int r) { return wr[32 * it + frow(r, h)]; }, Hn);
             __syncthreads();
 #pragma unroll
-            for (int r = 0; r < 16; ++r) H[r] = fmaxf(Hn[r], 0.0f);
+            for (int r = 0; r < 16; ++r) H[r] = relu(Hn[r]);
         }
         publish(X[w], l, H);
         __syncthreads();

@@ -9,7 +9,7 @@
 
 Both solve the same optimum (the best proper rotation) with Horn's quaternion
 method in f64 on the GPU; the reference's f32 torch results agree to f32
-rounding (tests/test_procrustes_golden.py pins this against fixtures generated
+rounding (tests/test_procrustes_gpu.py pins this against fixtures generated
 by importing the reference).
 """
 from __future__ import annotations
