@@ -785,6 +785,113 @@ int pcr_tfmr_select(const float *val, const int32_t *idx, const float *tgt, int3
                     int32_t m1, int32_t k, int32_t n_keep, int32_t *sel, float *w, float *tgt_corr,
                     int32_t *idx_keep, const void *scratch, pcr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Coherent Point Drift (Myronenko & Song 2010), the second alignment method of
+ * the reference (DataPreparation/CPD.py:26-73 runs probreg's RigidCPD, AffineCPD
+ * and NonRigidCPD on cupy in f32).  probreg is not available to this project, so
+ * the contract below is CPD as published with probreg's conventions as far as
+ * they are known; it is NOT pinned against probreg's own outputs.  The f64
+ * restatement is tests/cpd_ref.py.
+ *
+ * Layout.  src (P,Mmax,3) f32 is Y, the set that moves, with n_src (P) valid
+ *   points; tgt (P,Nmax,3) f32 is X with n_tgt (P).  n_src / n_tgt are device
+ *   arrays or NULL (= all Mmax / Nmax points).  Rows past a pair's count are
+ *   never read.  P <= 65535, Mmax, Nmax <= 2^24, 0 <= w < 1.
+ * E-step at a transform T and sigma2, per pair (M = n_src, N = n_tgt):
+ *   y^_m = (float)(T y_m), T applied in f64 as ((T0 x + T1 y) + T2 z) + T3;
+ *   d_mn = (dx dx + dy dy) + dz dz in f32, every operation rounded;
+ *   k_mn = exp(-d_mn / (2 sigma2)); c = (2 pi sigma2)^1.5 w / (1 - w) M / N;
+ *   den_n = sum_m k_mn, replaced by FLT_EPSILON where it is 0;
+ *   Pt1_n = den_n / (den_n + c); P1_m = sum_n k_mn / (den_n + c);
+ *   PX_m = sum_n k_mn x_n / (den_n + c); Np = sum_m P1_m.
+ *   A term whose argument is below -87 may be kept, flushed or skipped.
+ *   No (M,N) array is formed.  The kernels evaluate k as one exp2 of
+ *   fmaf(d, hi, d lo) with (hi, lo) the f32 pair of -log2(e) / (2 sigma2), add
+ *   terms in f32 in groups of four consecutive points ((k0 + k1) + (k2 + k3)),
+ *   the groups of a 512-point chunk in f64 in order, and the
+ *   chunks in f64 in order; 1 / (den_n + c) is rounded to f32 before the row
+ *   sums.  The row sweep sums, with v = k_mn / (den_n + c) in f32, the moments
+ *   sum v, sum v (y^_m - x_n) and sum v d_mn, which are of the size of the
+ *   residual and not of the clouds; P1_m = sum v and
+ *   PX_m = P1_m y^_m - sum v (y^_m - x_n) in f64, then rounded to f32.  Np adds
+ *   the f32 P1 in f64 (lane t of 256 adds t, t + 256, ...; halving tree).
+ *   That order does not depend on P or on how a launch is split, and
+ *   there are no float atomics: one call returns the same bytes every time and a
+ *   pair's result does not depend on what else is in the batch.
+ * Loop (pcr_cpd_register).  sigma2 starts at sum_mn |x_n - y_m|^2 / (3 M N) in
+ *   f64 (on the sources as given, not on init's image of them) and T at init
+ *   (P,16 row-major 4x4, rows 0..2 read) or the identity.  An iteration is the
+ *   E-step at (T, sigma2) and the M-step in f64 from the row sweep's f64
+ *   moments (P1, PX and sum_n v |x_n|^2 per source, before any rounding to f32):
+ *   mux = sum PX / Np, muy = Y^T P1 / Np, Yc = Y - muy,
+ *   A = PX^T Yc - mux (P1^T Yc), G = Yc^T dP1 Yc, and
+ *   trXPX = sum Pt1_n |x_n - mux|^2.  Over the targets some source reaches
+ *   (den_n != 0, where Pt1_n = sum_m v) it is evaluated as
+ *   sum_mn v |x_n|^2 - Np |mux|^2, i.e. under the same weights v as P1 and PX,
+ *   so that the residual below is a sum of squares under one set of weights and
+ *   keeps its digits when sigma2 is far below the clouds' extent; the targets
+ *   no source reaches (den_n = 0, v = 0 in every row) add their
+ *   Pt1_n |x_n - mux|^2 with Pt1_n = eps / (eps + c), in f64, in a pass over the
+ *   targets.  (That rule makes an outlier target pull sigma2 up once c falls
+ *   towards FLT_EPSILON, for w > 0 as for w = 0; it is the contract's.)
+ *   kind 0 (rigid): R = argmax tr(A^T R) over rotations (Horn's quaternion
+ *     method, the optimum U diag(1,1,det(U V^T)) V^T), s = 1,
+ *     sigma2 = (trXPX - 2 tr(A^T R) + tr G) / (3 Np);
+ *   kind 1 (rigid + scale): s = tr(A^T R) / tr G,
+ *     sigma2 = (trXPX - s tr(A^T R)) / (3 Np);
+ *   both: B = s R, t = mux - B muy,
+ *     q = (trXPX - 2 s tr(A^T R) + s^2 tr G) / (2 sigma2) + 1.5 Np ln sigma2;
+ *   kind 2 (affine): B = A G^-1, t = mux - B muy,
+ *     sigma2 = (trXPX - tr(A B^T)) / (3 Np),
+ *     q = (trXPX - 2 tr(A B^T) + tr(B G B^T)) / (2 sigma2) + 1.5 Np ln sigma2;
+ *   sigma2 is floored at FLT_EPSILON before q.  After the M-step of iteration
+ *   i >= 1 (0-based) a pair stops if |q_i - q_(i-1)| < tol; tol <= 0 never stops
+ *   (exactly maxiter iterations).  Every pair stops on its own and a stopped
+ *   pair's outputs no longer change.
+ *
+ * pcr_cpd_scratch_bytes: the bytes of the caller's scratch for these sizes, or
+ *   -1 on bad sizes.  No (M,N) array: the state records, inv, Pt1, P1, PX, the
+ *   five f64 row moments per source and one f64 per target, 256 + 56 Mmax +
+ *   16 Nmax bytes a pair.  On top of that, a sweep whose launch would have fewer than
+ *   512 workgroups (P ceil(lanes / 256) < 512: a small batch of large clouds) is
+ *   split over workgroups and keeps one f64 partial per lane and 512-point chunk
+ *   of the staged axis, not per slice, because that is what makes the sums'
+ *   order independent of P: 8 P Nmax ceil(Mmax / 512) bytes for the column sweep
+ *   and 40 P Mmax ceil(Nmax / 512) for the row sweep.  That term is a product
+ *   of both sizes.  It is bounded only by the split condition (P lanes < 131072):
+ *   1 MiB + 5 MiB at P = 1 and 8192 x 8192, about 0.9 GB at P = 1 and
+ *   100000 x 100000; batches of 512 / ceil(lanes / 256) pairs or more never pay it.
+ * pcr_cpd_estep: one E-step.  T (P,16) f64 or NULL (the sources are already
+ *   transformed; the non-rigid path); sigma2 (P) f64 device.  Outputs pt1
+ *   (P,Nmax), p1 (P,Mmax), px (P,Mmax,3) f32 and n_p (P) f64; a pair with an
+ *   empty cloud leaves its rows untouched.
+ * pcr_cpd_register: the loop, maxiter x (column sweep, row sweep, M-step)
+ *   enqueued on `stream` from a per-pair f64 state record in scratch; nothing
+ *   goes through the host, and the sequence can be captured in a graph.  When
+ *   the stream is not capturing and tol > 0, the count of stopped pairs is
+ *   read after every eighth iteration (one stream synchronisation) and the
+ *   launches left are dropped once every pair has stopped.  Outputs per pair:
+ *   T (16 f64 row-major, B in the 3x3 block), scale (s; 1 for kinds 0 and 2),
+ *   sigma2, q, iters (iterations run) and status: 0 ok; 1 n_src or n_tgt is 0
+ *   (the pair's other outputs are left alone); 2 sigma2 or q became non-finite
+ *   (the pair stops, T and scale keep the last finite iterate, sigma2 and q
+ *   report the values that ended it).  maxiter = 0 returns init and the initial
+ *   sigma2 with q = 0.
+ * scratch: pcr_cpd_scratch_bytes(P, Mmax, Nmax) bytes of device memory,
+ *   256-byte aligned.  All calls are asynchronous on `stream` except for the
+ *   read described above.
+ * ------------------------------------------------------------------------- */
+int64_t pcr_cpd_scratch_bytes(int32_t P, int32_t Mmax, int32_t Nmax);
+int pcr_cpd_estep(const float *src, const float *tgt, int32_t P, int32_t Mmax, int32_t Nmax,
+                  const int32_t *n_src, const int32_t *n_tgt, const double *T, const double *sigma2,
+                  double w, float *pt1, float *p1, float *px, double *n_p, void *scratch,
+                  pcr_stream_t stream);
+int pcr_cpd_register(const float *src, const float *tgt, int32_t P, int32_t Mmax, int32_t Nmax,
+                     const int32_t *n_src, const int32_t *n_tgt, int32_t kind, double w,
+                     int32_t maxiter, double tol, const double *init, double *T, double *scale,
+                     double *sigma2, double *q, int32_t *iters, int32_t *status, void *scratch,
+                     pcr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,15 +11,17 @@ reference's operator interfaces:
                  NgeNet's GCN
   matching       the similarity top-k matching of ROPNet's TFMRModule.forward
                  (similarity, row selection, weights and correspondences)
+  cpd            probreg.cpd's RigidCPD / AffineCPD / NonRigidCPD (Coherent
+                 Point Drift) with a matrix-free E-step, and a batched loop
 """
 from ._lib import PcrError, load as load_library  # noqa: F401
 
-__all__ = ["PcrError", "load_library", "grouping", "matching"]
+__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd"]
 
 
 def __getattr__(name):
     # the op modules import torch; the package itself (ABI loader) does not
-    if name in ("grouping", "matching"):
+    if name in ("grouping", "matching", "cpd"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

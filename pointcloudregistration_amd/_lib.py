@@ -106,6 +106,9 @@ SIGNATURES = {
     "pcr_edge_features": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p],
     "pcr_similarity_topk": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
     "pcr_tfmr_select": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p],
+    "pcr_cpd_estep": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _f64, _p, _p, _p, _p, _p, _p],
+    "pcr_cpd_register": [_p, _p, _i32, _i32, _i32, _p, _p, _i32, _f64, _i32, _f64, _p, _p, _p, _p, _p, _p, _p,
+                         _p, _p],
 }
 
 
@@ -151,6 +154,8 @@ def load():
         lib.pcr_ndp_chamfer_max_points.argtypes = []
         lib.pcr_tfmr_scratch_bytes.restype = _i64
         lib.pcr_tfmr_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32]
+        lib.pcr_cpd_scratch_bytes.restype = _i64
+        lib.pcr_cpd_scratch_bytes.argtypes = [_i32, _i32, _i32]
         lib.pcr_shutdown.restype = ctypes.c_int
         lib.pcr_shutdown.argtypes = []
         for name, args in SIGNATURES.items():
@@ -169,7 +174,7 @@ def exported_symbols():
     return ["pcr_last_error", "pcr_version", "pcr_workspace_release", "pcr_profile_enable", "pcr_profile_read",
             "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_ndp_train_partial_floats", "pcr_ndp_chamfer_scratch_bytes",
             "pcr_ndp_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words", "pcr_ndp_chamfer_max_points",
-            "pcr_tfmr_scratch_bytes", "pcr_shutdown"] + \
+            "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_shutdown"] + \
         list(SIGNATURES)
 
 
