@@ -1,4 +1,4 @@
-// Shared by the two feature-NN screens (featnn.hip: f16 x3 split, D <= 64;
+// Shared by the two feature-NN screens (featnn_v5.h and its units: f16 x3 split, D <= 64;
 // featnn_f32.hip: augmented f32 operands, 64 < D <= 128).
 #pragma once
 #include "pcr_internal.h"

@@ -1,0 +1,269 @@
+// The f16 x3 split feature screen (D <= 64), shared by its units: the operand
+// layout, the certification bounds, the kernels' argument structs and the host
+// entry points that cross units (featnn.hip has the map of the units).
+#pragma once
+#include "featnn_common.h"
+
+namespace pcr {
+
+struct Split5 {
+    int T;   // target exponent of max|x|
+    int cs;  // norm slot scale c = 2^cs
+};
+inline Split5 split5_params(int D) {
+    int L = 0;
+    while ((1 << L) < D) ++L;
+    Split5 s;
+    s.T = (30 - L) / 2 < 12 ? (30 - L) / 2 : 12;
+    s.cs = 2 * s.T + L - 15;
+    return s;
+}
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// v5: f16 x3 split screen on v_mfma_f32_32x32x16_f16 (32 cycles per 16-deep
+// k-step vs 64 per 2-deep step of the f32 MFMA: 7 instead of 17 x 4 cycles
+// per 32x32 tile at D = 32).
+//   scale: per pair x = f * 2^e (exact), e chosen so max|x| in [2^(T-1), 2^T)
+//          (T = 12 at D <= 64) -> every x fits f16 with room for the products.
+//   split: x = hi + lo + e_x, hi = f16(x), lo = f16(x - hi): |e_x| <= 2^-22|x|
+//          + 2^-14 (the 2^-14 covers f16 subnormals even if flushed).
+//   operands (k order, each D-segment padded to S = ceil(D/16) chunks of 16):
+//          A_i = [-2hi | -2hi | -2lo | nx_hi nx_mid nx_lo | c c c | 0 | 2^15]
+//          B_j = [  hi |   lo |   hi | c c c | ny_hi ny_mid ny_lo | 2^15 | 0]
+//          (norm chunk k = 6 / k = 7: the bias slots.  The G image (role 1)
+//          stores 2^15 at k = 6, the F image (role 0) at k = 7; featnn_row8
+//          patches the row operand's opposite slot in registers -- 1.0 at k = 6
+//          for pass 1 (F rows), k = 7 for pass 2 (G rows), 64 for the 1-term
+//          screens -- see kRowBias / kRowBias1)
+//          nx = |x|^2 / c split into three f16 parts, c = 2^cs fits f16.
+//          Executed: NX = 3S + 1 k-chunks (one MFMA each).  Stored: NM = 2S + 1
+//          -- A as [-2hi | -2lo | norms], B as [hi | lo | norms]; the MFMA of
+//          chunk c reads A chunk amap(c) and B chunk bmap(c) (the repeated
+//          segment is the same registers), so the packed operands, the
+//          L2 -> LDS stream and the B-fragment LDS reads are 5/7 of the
+//          executed k at D = 32.
+//   C = 0 -> d'_ij = |x_i|^2 + |y_j|^2 - 2 x_i.y_j (scaled by 2^2e) with
+//   |d' - d'_exact| <= err(q, G) (bound5 below).  Products are exact in f32;
+//   the accumulation is charged 2 (Kt + 2) u (|x| + |y|)^2 whatever the
+//   MFMA's internal summation order.  Rows/columns whose top-2 gap is not
+//   above 2 err are rescanned exactly in f64 (featnn_rescan2).
+// Packed layout: [pair][tile][stored chunk][lane] of 8 halves (lane l: row/col l&31,
+// k = 16 chunk + 8 (l>>5) + j); padded tiles are valid encodings of +inf
+// rows, so no loop has a tail.  Grid: 1-D, XCD-aware: all row blocks of a
+// pair run on one XCD, whose L2 then holds that pair's B image (1.8 MB).
+// ---------------------------------------------------------------------------
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// executed k-chunk c -> stored A / B chunk (see the operand layout above)
+__host__ __device__ constexpr int amap(int c, int S) { return c < S ? c : (c < 3 * S ? c - S : 2 * S); }
+__host__ __device__ constexpr int bmap(int c, int S) { return c < 2 * S ? c : (c < 3 * S ? c - 2 * S : 2 * S); }
+
+__device__ __forceinline__ float pair_scale5(unsigned mbits, int T) {
+    const int E = (int)((mbits >> 23) & 0xff);
+    if (E == 0 || E == 255) return 1.0f;
+    const int e = min(max(T + 126 - E, -126), 127);
+    return __int_as_float((e + 127) << 23);
+}
+
+// Where a pack launch takes its pairs and their scale (see feat_sample):
+// normal: grid.y = P, the pair's sample max with kSpecMargin binades of
+// headroom, rows outside the split's range flag the pair; repair: grid.y =
+// kRepairR, the flagged pairs by rank, the full max from feat_maxabs.
+struct PackCtl {
+    const unsigned *smax;  // [P] sample max bits (normal)
+    const unsigned *mxp;   // [P][2][Z] full partial maxima (repair)
+    int Z, P, repair;
+    int *bad;              // [P] flags
+    unsigned *sc;          // [P] the scale used (f32 bits), for the rescans
+};
+
+// both clouds in one launch: blockIdx.z = role (0: F as rows, 1: G as columns)
+struct PackIO {
+    const float *X[2];
+    const int32_t *n[2];
+    int Nmax[2], ntiles[2];
+    f16x8 *Xp[2];
+    float *nrm[2];
+    unsigned *nmax[2];
+    unsigned *emax[2];  // per pair: max over the cloud's rows of |x s - f16(x s)| (the 1-term screen's bound)
+    float *rex[2];      // per row: its |x s - f16(x s)| (rounded up; featnn_regroup9's bound)
+    float *ct[2];       // per row: f32(|x s|^2), -1 on padding rows (feat_colterms adds the bias)
+};
+
+// |x - f16(x)| of one row (x already scaled), rounded up: e^2 summed exactly
+// enough in f64 (each term exact), the sqrt's rounding covered by the factor
+__device__ __forceinline__ float split_err_norm(double e2) {
+    return (float)(__builtin_sqrt(e2) * (1.0 + 1e-6));
+}
+
+// certification threshold for a top-2 gap in scaled units (see header)
+__device__ __forceinline__ double bound5(double q, double G, int Kt, int D) {
+    const double u = 5.9604644775390625e-08;  // 2^-24
+    const double qg = q + G;
+    const double err = 2.0 * (Kt + 2) * u * qg * qg + 6.0 * 2.384185791015625e-07 * q * G +
+                       1.220703125e-04 * __builtin_sqrt((double)D) * qg +
+                       1.1641532182693481e-10 * (q * q + G * G) + 4.0;
+    return 2.0 * err;
+}
+
+struct DualArgs5 {
+    const f16x8 *Ap, *Bp;
+    const float *fnr, *gnr;  // scaled norms
+    const unsigned *fmax, *gmax;
+    const int32_t *n_src, *n_tgt;
+    int P, Nmax, Mmax, ntn, ntm, nrb, D, ctbits;
+    int32_t *nn12;
+    int *list12, *count12;
+    float *cp1, *cp2;
+    int *cpi;
+};
+
+// column tiles per LDS group of featnn_row8 / featnn_row9 (v5_prepare pads the
+// column images to whole groups of both)
+constexpr int kRow8G = 8;      // column tiles per LDS group (16: the whole LDS, measured no faster)
+#ifndef PCR_ROW9_G
+#define PCR_ROW9_G 16  // 8: pass 1 1.12 vs 1.09 ms, pass 2 0.76 vs 0.74 (C4, featnn_bench)
+#endif
+#ifndef PCR_ROW9_G1
+#define PCR_ROW9_G1 PCR_ROW9_G
+#endif
+constexpr int kRow9G = PCR_ROW9_G;     // featnn_row9's: pass 2 (and the padding)
+constexpr int kRow9G1 = PCR_ROW9_G1;   // pass 1 (<= kRow9G)
+// B: pass 1 1.0 (row k = 6) x 2^15 (G's column image, k = 6); pass 2 (featnn_row8
+// <.., false>, the J rows of G against F's image) 1.0 (row k = 7) x 2^15 (F's
+// image, k = 7).  dual7 pairs F's image with G's: 0 x 2^15 at both slots.
+constexpr double kRowBias = 32768.0;
+constexpr double kRowBias1 = 2097152.0;  // 2^21: the 1-term screens' (featnn_row8<.., kOne>, see there)
+
+// certification threshold of the 1-term screen (scaled units), 2 x the error
+// bound; ex, E: the row's and the columns' max |x - f16(x)|, subnormal term added
+__device__ __forceinline__ double bound1(double q, double ex, double G, double E, int Kt) {
+    const double u = 5.9604644775390625e-08;  // 2^-24
+    const double qg = q + G;
+    const double err = 2.0 * (Kt + 2) * u * qg * qg + 2.0 * (ex * G + (q + ex) * E) +
+                       1.1641532182693481e-10 * (q * q + G * G) + 4.0;
+    return 2.0 * err;
+}
+__device__ __forceinline__ double sub_term(int D) { return 6.103515625e-05 * __builtin_sqrt((double)D); }  // 2^-14 sqrt(D)
+
+struct MutArgs {
+    const int32_t *nn12, *n_src, *n_tgt;
+    int Nmax, Mmax, mutual, ransac_n, Kt, D, ntm;
+    int *used;        // [P][Mmax + 1]: 1 = j in J (2: listed for the rescan), 3: listed, not in J
+    int *pos;         // [P][Mmax + 1] scan scratch
+    int *jlist, *nj;  // [P][Mmax], [P]: the rows of pass 2, ascending
+    const double *v12;
+    const float *e12;
+    const float4 *wq;   // (w1, w2, e2, the bias in w1 / w2)
+    const unsigned *fmax;
+    const int32_t *nns; // the screened argmins J is built from (never overwritten by the rescans)
+    const float *F, *G; // the f32 clouds and the scale the packs used: the exact distance of a
+    const unsigned *mx; // candidate whose screened value is too coarse for its column's gap
+    int *flag;        // [P][Nmax + 1]: mutual 0 / 1, 2 = decided by the exact column
+    int *list21, *cnt21;
+    const int32_t *nn21x;
+    int32_t *corres, *n_corres;
+};
+
+}  // namespace
+
+struct RescanArgs5 {
+    const float *F, *G;
+    const int32_t *n_src, *n_tgt;
+    int Nmax, Mmax, D;
+    const int *list12, *list21, *cnt12, *cnt21;
+    int32_t *nn12, *nn21;
+    // candidate slices (gridDim.z = S): the first `cap` listed rows of a pair and
+    // direction are scanned by S blocks over disjoint candidate ranges, each
+    // writing its lexicographic (d, j) minimum to slot (p, dir, e, s), merged by
+    // featnn_rescan_merge; rows past `cap` are scanned whole by slice 0
+    int cap;
+    double *sd;
+    int *sj;
+    // mutual path (feature_corres_v5): the exact distance of a rescanned F row,
+    // in the screen's scaled units (x s^2, s = pair_scale5(mx[p], T): a power of
+    // two, exact), and its error 0; null elsewhere
+    double *v12;
+    float *e12;
+    const unsigned *mx;
+    int T;
+};
+
+// the row screens' arguments (the mutual path: feature_corres_v5 in featnn.hip)
+struct RowArgs5 {
+    const f16x8 *Ap;            // row operand (register-resident): [P][ntr][NM][64]
+    const f16x8 *Bp;            // column operand (LDS-streamed): [P][ntc][NM][64]
+    const float *rnr;           // scaled row norms, [P][ntr * 32] by original row index
+    const unsigned *cmax;       // per pair max scaled column norm (f32 bits)
+    const int32_t *n_rows, *n_cols;
+    const int *rlist, *rcount;  // pass 2: rows rlist[p][0 .. rcount[p]) (original indices)
+    int P, Rmax, Cmax, ntr, ntc, nrb, D, ctbits;
+    int32_t *nn;                // pass 1: argmin (screened), value, its error, uncertified rows
+    double *v;
+    float *e;
+    int *list, *count;
+    float4 *wq;                 // pass 2: (top-2 values, the screen's error bound, -) by original row index
+    // pass 2: the gathered rows built in registers from the f32 cloud (one
+    // 128-byte row per lane instead of ten 16-byte pieces in ten lines of the
+    // packed image), with the scale the packs used and the image's role
+    const float *Xr;
+    const unsigned *sc;
+    int role, cs;
+    const unsigned *cemax;      // featnn_row8<.., kOne>: per pair max |y - f16(y)| of the column image
+    int32_t *nns;               // pass 1: a copy of the screened argmin for featmut_jbuild (nullable)
+    int fbdiag;                 // 1 / 2: count the listed rows in g_featnn_fallback_rows[0 / 1]
+    int rbmajor;                // featnn_row8: blocks ordered row block first (short lists, below)
+    const float *rre;           // the rows' |x - f16(x)| from the pack, [P][ntr * 32]
+    // featnn_row9's buckets (rows by winning step): [P][steps] counts and
+    // [P][steps][bcap] entries (row, B1, B2, lane half of the winning group)
+    int *bcnt, bcap;
+    uint4 *blist;
+    uint4 *rec;                 // featnn_regroup9 -> featnn_finish9, by row: (column, B1, B2, skip)
+    int *llist, *lcount;        // featnn_finish9: where its failing rows go (nullable)
+    // featnn_row8 list mode over column slices (csl > 1: short lists at small
+    // batches): slice sl's partial (B1, B2, column) per listed row position k,
+    // [P][csl][Rmax], merged by featnn_slicemerge
+    int csl;
+    uint4 *part;
+    // featnn_row9: the column cloud's and the row cloud's per-row terms
+    // f32(|.|^2 + B) ([P][ntc * 32], [P][ntr * 32]) and B
+    const float *cct, *rct;
+    const float *cbias;  // [P] B
+};
+
+// packed operands, norms and per-pair maxima of both clouds (shared by the
+// dual screen and the mutual path)
+struct V5Buf {
+    int S, NM, NX, W, nrb, ntn, ntm, ctbits;  // S chunks per D-segment, NM stored, NX executed
+    Split5 sp;
+    f16x8 *Ap, *Bp;
+    float *fnr, *gnr;
+    unsigned *gmax, *fmax, *mx;
+    int *cnt12, *cnt21, *list12, *list21;
+    unsigned *gemax, *femax;  // per pair max |x - f16(x)| of the column (G) / row (F) images
+    int *fbc12, *fbc21, *fbl12, *fbl21;  // the rows a 1-term screen left for the 3-term one
+    float *fre, *gre;                    // per row |x - f16(x)| of F / G (scaled, rounded up)
+    float *fct, *gct;                    // per row f32(|x|^2 + B) of F / G (featnn_row9's column terms)
+    float *cbias;                        // [P] their B (feat_colterms)
+};
+
+// featnn_pack.hip
+int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D, const int32_t *n_src,
+               const int32_t *n_tgt, hipStream_t s, V5Buf &v);
+// featnn_dual.hip
+int feature_match_v5(const float *F, const float *G, int P, int Nmax, int Mmax, int D, const int32_t *n_src,
+                     const int32_t *n_tgt, int32_t *nn12, int32_t *nn21, hipStream_t s);
+// featnn_rescan.hip
+RescanArgs5 rescan_args(const float *F, const float *G, const int32_t *n_src, const int32_t *n_tgt, int Nmax,
+                        int Mmax, int D);
+int run_rescan(RescanArgs5 &ra, int P, int D, hipStream_t s);
+// featnn_row.hip (instantiated there for every kIdx / kOne); each sets its own r.nrb
+constexpr int kRegroupMaxSteps = 4096;  // featnn_regroup9 keeps a pair's per-step prefix in LDS
+template <bool kIdx> int launch_row7(const RowArgs5 &r, int S, hipStream_t s);  // S = 3, 4
+template <bool kIdx, bool kOne> int launch_row8(const RowArgs5 &r, int S, hipStream_t s);
+template <bool kIdx> int launch_row9(const RowArgs5 &r, int S, hipStream_t s);
+template <bool kIdx> int launch_regroup9(const RowArgs5 &r, int S, hipStream_t s);
+
+}  // namespace pcr

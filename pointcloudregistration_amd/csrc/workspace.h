@@ -17,20 +17,20 @@ enum WsSlot : int {
     kWsNone = -1,                 // fpfh.hip run_search: "no list slot" (the caller's own buffers)
     kWsNndPartials = 0,           // nnd.hip: split sweep's partial (dist, idx); pcr_nnd_forward
     kWsNndBackward = 1,           // nnd.hip: counts, starts, sorted lists; pcr_nnd_backward
-    kWsFeatPack_NndRagged = 2,    // featnn.hip v5_prepare / featnn_f32.hip: packed descriptors, norms, lists
+    kWsFeatPack_NndRagged = 2,    // featnn_pack.hip v5_prepare / featnn_f32.hip: packed descriptors, norms, lists
                                   // (exclusive branches of one call, D <= 64 / D > 64); nnd_ragged.hip:
                                   // partials of pcr_nnd_forward_ragged, another ABI call
     kWsCorres = 3,                // featnn.hip corres_impl: corres_build's scratch; pcr_correspondences, D > 64
     kWsRansacGrid = 4,            // ransac.hip build_ransac_grids: target grids (pipeline: side stream)
     kWsFpsOver_PpfIdx = 5,        // group.hip: pcr_fps's distances past the registers; pcr_group_ppf's
                                   // neighbour indices -- two ABI calls
-    kWsFeatRescan = 6,            // featnn.hip run_rescan: slice partials (d, j); stream-ordered reuse in a call
+    kWsFeatRescan = 6,            // featnn_rescan.hip run_rescan: slice partials (d, j); stream-ordered reuse in a call
     kWsIcpGrid = 7,               // icp.hip / pipeline.cpp: ICP's target grid (pipeline: side stream, for icp_impl)
     kWsIcpPoints = 8,             // icp.hip: f64 working copy of the sources
     kWsRegister = 9,              // pipeline.cpp: nn12 | nn21 | corres | n_corres; pcr_register_feature_ransac
     kWsIcpPartials_RadiusNnGrid = 10,  // icp.hip: cooperative partial sums; grid.hip: pcr_radius_nn's grid,
                                        // an ABI call that runs no ICP
-    kWsFeatDualCols = 11,         // featnn.hip feature_match_v5 / featnn_f32.hip: dual screen's column partials
+    kWsFeatDualCols = 11,         // featnn_dual.hip feature_match_v5 / featnn_f32.hip: dual screen's column partials
                                   // (exclusive branches, D <= 64 / D > 64); pcr_feature_match, D > 64 corres
     kWsIcpTiming = 12,            // icp.hip: PCR_ICP_TIMING clocks
     kWsRansacOrder = 13,          // ransac.hip / pipeline.cpp: spatial order of the sources (pipeline: built on

@@ -1,5 +1,5 @@
 """Inputs and a numpy model for the tests of the 1-term feature screen's bias and
-certificates (csrc/featnn.hip: feat_sample / feat_pack5 / feat_colterms /
+certificates (csrc/featnn_pack.hip, featnn_row.hip: feat_sample / feat_pack5 / feat_colterms /
 row_tail).  No GPU here: test_featscreen_model_cpu.py checks on any machine that
 the generated cases are adversarial, the *_gpu.py files run them.
 
@@ -23,7 +23,7 @@ def split5_params(D):
 
 
 def pair_scale5(m, T):
-    """featnn.hip pair_scale5: 2^e with max * 2^e in [2^(T-1), 2^T)."""
+    """featnn_v5.h pair_scale5: 2^e with max * 2^e in [2^(T-1), 2^T)."""
     bits = int(np.float32(m).view(np.uint32))
     E = (bits >> 23) & 0xff
     if E == 0 or E == 255:

@@ -1,5 +1,5 @@
 """GPU: pcr_feature_correspondences, the mutual feature matching without nn21
-for every target (csrc/featnn.hip featnn_row7: the rows screened with their
+for every target (csrc/featnn.hip feature_corres_v5, csrc/featnn_row.hip: the rows screened with their
 argmin, the targets some source picked screened for top-2 values only, each
 candidate decided from certified values or the exact column rescan).
 
@@ -334,7 +334,7 @@ def test_feature_correspondences_row8_one_term(oracle, monkeypatch, name):
 
 def test_colterm_bias_per_pair(oracle):
     """featnn_row9's column terms ct = f32(|y|^2 + B) with B the pair's power of
-    two above BOTH clouds' max |x|^2 (feat_colterms, csrc/featnn.hip): pairs whose
+    two above BOTH clouds' max |x|^2 (feat_colterms, csrc/featnn_pack.hip): pairs whose
     clouds differ by decades in norm (B set by the rows in pass 1, by the columns
     in pass 2), a single huge-norm row, an all-zero target cloud but one row (B
     near 1), tiny descriptors (the pair scale lifts them) -- in one batch, every

@@ -1,4 +1,4 @@
-"""GPU: the 1-term feature screen's bias B (feat_colterms, csrc/featnn.hip) at the
+"""GPU: the 1-term feature screen's bias B (feat_colterms, csrc/featnn_pack.hip) at the
 inputs where the unsigned order of its values can break.
 
 featnn_row9's values are ct_j - 2 f16(x).f16(y_j), ct_j = f32(|y_j|^2 + B), and

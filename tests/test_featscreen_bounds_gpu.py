@@ -1,6 +1,6 @@
 """GPU: the feature screen's certificates against exact distances.
 
-row_tail (csrc/featnn.hip) stores for every pass-1 row its screened value and an
+row_tail (csrc/featnn_row.hip) stores for every pass-1 row its screened value and an
 error bound, v12 / e12, and for every pass-2 column wq = (w1 + bias, w2 + bias,
 e2, bias); featmut_resolve decides mutuality from these numbers alone.  Here
 they are read back (pcr_featmut_debug_copy, the layout of feature_corres_v5's
