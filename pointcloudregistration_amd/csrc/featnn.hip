@@ -17,6 +17,7 @@
 //   featnn_pack.hip    scale, packed operands, norms, column terms   (v5_prepare)
 //   featnn_dual.hip    both directions in one screen                 (feature_match_v5)
 //   featnn_row.hip     one direction's rows: featnn_row7 / row8 / row9 (launch_row*)
+//   featnn_thresh.hip  featnn_row9's leftover rows from threshold candidates (launch_thresh9)
 //   featnn_rescan.hip  exact f64 rescan of the uncertified           (run_rescan)
 //   featnn.hip         this file: the mutual path's driver and kernels, the C entry points
 //   featnn_f32.hip     64 < D <= 128: augmented f32 operands on v_mfma_f32_32x32x2_f32
@@ -248,6 +249,14 @@ static int beside(hipStream_t s, Side side, Main main) {
     return PCR_OK;
 }
 
+// the threshold route behind featnn_row9 (featnn_thresh.hip): on by default,
+// PCR_FEAT_THRESH=0 for the 3-term screens of its leftover rows (A/B, parity;
+// read per call)
+static bool feat_thresh() {
+    const char *e = getenv("PCR_FEAT_THRESH");
+    return !(e && e[0] == '0');
+}
+
 // the 1-term screens in front of the 3-term ones (S <= 2): on by default,
 // PCR_FEAT_ONE=0 for the round-5 path (A/B, the parity tests; read per call)
 static bool feat_one_term() {
@@ -283,15 +292,31 @@ static bool feat_one_term() {
 //   one     featnn_row8's 1-term pass, then the 3-term screen of the rows it listed;
 //   S <= 2  the 3-term featnn_row8 alone;  S > 2  featnn_row7.
 // r: the pass's screen; fb: its 3-term fallback over the list r fills.
+// th (use9 only, null with PCR_FEAT_THRESH=0): the threshold route instead of
+// the 3-term screen -- the finish appends its failing rows to the sweep's own
+// list, then featnn_thresh9 + featnn_exact_cand settle that list (in `slot_fb`),
+// all in order on s; th->llist / lcount take the rows they leave (pass 1).
 template <bool kIdx>
 static int run_pass(const RowArgs5 &r, const RowArgs5 &fb, int S, bool one, bool use9, int slot, int slot_fb,
-                    int *llist, int *lcount, hipStream_t s) {
+                    int *llist, int *lcount, hipStream_t s, const RowArgs5 *th = nullptr) {
     int rc;
     prof_begin(s, slot);
     if (use9) {
         PCR_HIP_CHECK(hipMemsetAsync(r.bcnt, 0, sizeof(int) * (size_t)r.P * (r.ntc / 2), s));  // a count per step
         if ((rc = launch_row9<kIdx>(r, S, s)) != PCR_OK) return rc;
         prof_end(s, slot);
+        if (th) {
+            RowArgs5 rg = r;
+            rg.llist = r.list; rg.lcount = r.count; rg.thresh = 1;
+            prof_begin(s, kProfFeatRegroup);
+            rc = launch_regroup9<kIdx>(rg, S, s);
+            prof_end(s, kProfFeatRegroup);
+            if (rc != PCR_OK) return rc;
+            prof_begin(s, slot_fb);
+            rc = launch_thresh9<kIdx>(*th, S, s);
+            prof_end(s, slot_fb);
+            return rc;
+        }
         RowArgs5 rg = r;
         rg.llist = llist; rg.lcount = lcount;
         return beside(s, [&](hipStream_t q) { return launch_fallback<kIdx>(fb, S, q, slot_fb); },
@@ -336,11 +361,15 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
     const size_t pr = (size_t)P * std::max(Nmax, Mmax);
     const int fsl = list_slices(P);
     const size_t pt = fsl > 1 ? (size_t)fsl * pr : 0;  // the sliced 3-term screens' partials
+    const bool one = v.S <= 2 && feat_one_term();
+    // (the regroup keeps a pair's per-step prefix in LDS)
+    const bool use9 = one && feat_row9() && std::max(ntm, ntn) / 2 <= kRegroupMaxSteps;
+    const bool thresh = use9 && feat_thresh();
     MutArgs ma;
     double *v12;
     float *e12;
     float4 *wq;
-    int *nn21x, *zero, *bcnt;
+    int *nn21x, *zero, *bcnt, *cand;
     int32_t *nns;
     uint4 *blist, *rec, *part;
     WsLayout l;  // pcr_featmut_debug_copy's readers go by these offsets
@@ -354,13 +383,11 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
     l.take(blist, pl);  // 16-byte aligned
     l.take(rec, pr); l.take(part, pt);
     l.take(bcnt, pb);
+    l.take(cand, thresh ? pr * kThreshK : 0);  // featnn_thresh9's candidate slots
     bool fresh = false;
     // + 32: the tail also keeps 16 bytes per round-up (wq, blist) beyond the layout's own padding
     PCR_REQUIRE(workspace_bind(kWsFeatMutual, l, kWsSlack + 32, &fresh), PCR_ERR_NOMEM, "feature_corres: %s",
                 pcr_last_error());
-    const bool one = v.S <= 2 && feat_one_term();
-    // (the regroup keeps a pair's per-step prefix in LDS)
-    const bool use9 = one && feat_row9() && std::max(ntm, ntn) / 2 <= kRegroupMaxSteps;
     // a constant zero count per pair (read only): cleared when the slot is new
     // or was last used for fewer pairs
     static thread_local const void *z_ptr = nullptr;
@@ -392,6 +419,7 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
     r.rre = v.fre; r.bcnt = bcnt; r.blist = blist; r.bcap = cap1; r.rec = rec;
     r.cct = v.gct; r.rct = v.fct; r.cbias = v.cbias;
     r.csl = 1; r.part = part; r.llist = nullptr; r.lcount = nullptr;
+    r.thresh = 0; r.cand = cand; r.used = nullptr; r.Xc = G; r.fbctr = nullptr; r.dbg = 0;
     auto prep_hook = [&](int at) -> int {
         if (!prep_event || prep_at != at) return PCR_OK;
         PCR_HIP_CHECK(hipEventRecord(prep_event, s));
@@ -401,8 +429,15 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
     };
     if ((rc = prep_hook(2)) != PCR_OK) return rc;
     // (the regroup's failing rows go to the exact rescan's list: the 3-term screen runs beside it)
+    // the threshold route's view of a pass: the rows r lists; what it leaves goes to list / count
+    auto thresh_args = [](RowArgs5 t, int *list, int *count) {
+        t.rlist = t.list; t.rcount = t.count;
+        t.llist = list; t.lcount = count;
+        return t;
+    };
+    const RowArgs5 t1 = thresh_args(r, v.list12, v.cnt12);
     rc = run_pass<true>(r, fallback_args(r, v.list12, v.cnt12, 1, fsl), v.S, one, use9, kProfFeatScreen,
-                        kProfFeatScreen1b, v.list12, v.cnt12, s);
+                        kProfFeatScreen1b, v.list12, v.cnt12, s, thresh ? &t1 : nullptr);
     if (rc != PCR_OK) return rc;
     if ((rc = prep_hook(1)) != PCR_OK) return rc;
     RescanArgs5 ra = rescan_args(F, G, n_src, n_tgt, Nmax, Mmax, D);
@@ -459,7 +494,11 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
         const RowArgs5 r2b = fallback_args(r2, nullptr, nullptr, 2, fsl);
         if (use9) { r2.rre = v.gre; r2.bcap = cap2; r2.cct = v.fct; r2.rct = v.gct; }
         // (no list for the finish: the resolve sends an undecided column to the exact column rescan)
-        rc = run_pass<false>(r2, r2b, v.S, one, use9, kProfFeatScreen2, kProfFeatScreen2b, nullptr, nullptr, s);
+        // (the threshold route: the exact argmin of a settled column goes to nn21x, its flag to 2)
+        RowArgs5 t2 = thresh_args(r2, nullptr, nullptr);
+        t2.nn = nn21x; t2.used = ma.used; t2.Xc = F;
+        rc = run_pass<false>(r2, r2b, v.S, one, use9, kProfFeatScreen2, kProfFeatScreen2b, nullptr, nullptr, s,
+                             thresh ? &t2 : nullptr);
         if (rc != PCR_OK) return rc;
         if (rs != s) PCR_HIP_CHECK(hipStreamWaitEvent(s, ev_join, 0));
         hipLaunchKernelGGL(featmut_resolve, dim3(cdiv(Nmax, 256), P), dim3(256), 0, s, ma);

@@ -327,9 +327,6 @@ __global__ __launch_bounds__(512) void featnn_row7(RowArgs5 a) {
 // ---------------------------------------------------------------------------
 constexpr int kRow8Head = 24;  // epilogue VALU in front of phase A's first MFMA (the B reads' latency)
 
-__device__ __forceinline__ unsigned umin2(unsigned a, unsigned b) { return a < b ? a : b; }
-__device__ __forceinline__ unsigned umax2(unsigned a, unsigned b) { return a > b ? a : b; }
-
 // The 1-term screen (round 6, kOne): the row operand is -2 f16(x) and the column
 // operand f16(y) -- one k-segment instead of the split's three (hi.hi', hi.lo',
 // lo.hi'), so S + 1 MFMAs per 32 x 32 tile instead of 3 S + 1, and the column
@@ -384,9 +381,7 @@ __device__ __forceinline__ bool row_tail(const RowArgs5 &a, int p, int row, int 
     if constexpr (kCT) {
         const double ex = (double)rexv + sub, E = (double)__uint_as_float(a.cemax[p]) + sub;
         const double B = (double)a.cbias[p];
-        const double err = 2.0 * (16 * NX + 2) * u * ((B + Gm * Gm) + 2.0 * (qn + ex) * (Gm + E)) +
-                           2.0 * (ex * Gm + (qn + ex) * E) + u * (2.0 * B + Gm * Gm) * (1.0 + 0x1p-20) + 4.0;
-        bnd = 2.0 * err;
+        bnd = bound_ct(qn, ex, Gm, E, B, 16 * NX);
         bias = 2.0 * B - (double)ctr;
         ebias = u * (2.0 * B + qn * qn) * (1.0 + 0x1p-20);
     } else {
@@ -456,8 +451,7 @@ __device__ __forceinline__ bool one_term_fails(const RowArgs5 &a, int p, int row
     const double Gm = (double)__uint_as_float(a.cmax[p]);
     const double ex = (double)rexv + sub, E = (double)__uint_as_float(a.cemax[p]) + sub;
     const double B = (double)a.cbias[p];
-    const double bnd = 2.0 * (2.0 * (16 * NX + 2) * u * ((B + Gm * Gm) + 2.0 * (qn + ex) * (Gm + E)) +
-                              2.0 * (ex * Gm + (qn + ex) * E) + u * (2.0 * B + Gm * Gm) * (1.0 + 0x1p-20) + 4.0);
+    const double bnd = bound_ct(qn, ex, Gm, E, B, 16 * NX);
     const double ebias = u * (2.0 * B + qn * qn) * (1.0 + 0x1p-20);
     if constexpr (!kIdx) return !(mb2 - mb1 > (bnd + 2.0 * ebias) * (1.0 + 1e-6) + 1e-6 * mb1);
     const double dot = 2.0 * (ex * Gm + (qn + ex) * E);
@@ -774,60 +768,6 @@ __global__ __launch_bounds__(256) void featnn_slicemerge(RowArgs5 a) {
 // broadcasts of one float per lane (see the sweep).
 // ---------------------------------------------------------------------------
 
-// The 1-term row operand of one row (lane half h) built from its f32 values:
-// its -2 f16(x) chunks exactly as the packs store them (row_frags) -- one
-// 128-byte line per row where the packed image spreads it over S lines: the
-// regroup gathers rows.  The sweep and the regroup both build it here, so
-// their MFMA chains agree bit for bit.  (No norm chunk: featnn_row9 takes the
-// columns' |y|^2 + B as the MFMA's accumulator input and leaves |x|^2 out.)
-template <int S>
-__device__ __forceinline__ void row_operand1(const RowArgs5 &a, int p, int row, bool valid, int h,
-                                             f16x8 (&A)[S]) {
-    const float sc = __uint_as_float(a.sc[p]);
-    float x[16 * S];
-    const float *xr = a.Xr + ((size_t)p * a.Rmax + row) * a.D;
-    if (valid && a.D == 16 * S && ((uintptr_t)xr & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < 4 * S; ++q) {
-            const float4 v = reinterpret_cast<const float4 *>(xr)[q];
-            x[4 * q] = v.x * sc; x[4 * q + 1] = v.y * sc; x[4 * q + 2] = v.z * sc; x[4 * q + 3] = v.w * sc;
-        }
-    } else if (valid) {
-#pragma unroll
-        for (int q = 0; q < 16 * S; ++q) x[q] = q < a.D ? xr[q] * sc : 0.0f;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 16 * S; ++q) x[q] = 0.0f;
-    }
-    // both lane halves' elements at compile-time indices, then the half's pick
-    // (an index by h is a select chain over the row)
-    auto seg = [&](int k) {
-        const _Float16 hi = (_Float16)x[k];
-        return k < a.D ? (a.role == 0 ? (_Float16)(-2.0f * (float)hi) : hi) : (_Float16)0.0f;
-    };
-#pragma unroll
-    for (int c = 0; c < S; ++c)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const _Float16 v0 = seg(16 * c + j), v1 = seg(16 * c + 8 + j);
-            A[c][j] = h ? v1 : v0;
-        }
-}
-
-// a lane's 16 column terms of column tile ct (register r: column
-// 8 (r / 4) + 4 h + (r % 4)), from 32 floats per tile
-__device__ __forceinline__ f32x16 colterms(const float *tile32, int h) {
-    f32x16 c;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float4 v = *reinterpret_cast<const float4 *>(tile32 + 8 * j + 4 * h);
-        c[4 * j] = v.x; c[4 * j + 1] = v.y; c[4 * j + 2] = v.z; c[4 * j + 3] = v.w;
-    }
-    return c;
-}
-
-__device__ __forceinline__ unsigned fbits(float v) { return __float_as_uint(v); }
-
 // min of a lane's 32 values of one step (two column tiles): three v_min3 chains
 __device__ __forceinline__ unsigned group_min32(const f32x16 &x, const f32x16 &y) {
     unsigned c0 = umin2(umin2(fbits(x[0]), fbits(x[1])), fbits(x[2]));
@@ -1056,7 +996,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void f
             if (rank < a.bcap) {
                 a.blist[bk * a.bcap + rank] = make_uint4((unsigned)row, w1, s2, mine ? 0u : 1u);
             } else {
-                a.rec[(size_t)p * a.Rmax + row] = make_uint4(0u, 0u, 0u, 1u);
+                // (a zero counter, B1 and no column yet: featnn_thresh9's inputs)
+                a.rec[(size_t)p * a.Rmax + row] = make_uint4(0u, w1, 0xffffffffu, 1u);
                 a.list[(size_t)p * a.Rmax + atomicAdd(a.count + p, 1)] = row;
             }
         }
@@ -1218,6 +1159,9 @@ __global__ __launch_bounds__(256) void featnn_finish9(RowArgs5 a) {
                                                    a.rre[(size_t)p * a.ntr * 32 + rows[i]], 0.0,
                                                    a.rct[(size_t)p * a.ntr * 32 + rows[i]]);
         mine += put[i] ? 1 : 0;
+        // the threshold route lists them with the sweep's own: marked alike
+        if (put[i] && a.thresh && a.llist)
+            a.rec[(size_t)p * a.Rmax + rows[i]] = make_uint4(0u, rc[i].y, 0xffffffffu, 1u);
     }
     // block-wide exclusive offsets of the listed rows
     int x = mine;
@@ -1319,6 +1263,12 @@ int launch_regroup9(const RowArgs5 &r, int S, hipStream_t s) {
         hipLaunchKernelGGL((featnn_finish9<2, kIdx>), fgrid, dim3(256), 0, s, r);
     }
     PCR_LAUNCH_CHECK();
+    return PCR_OK;
+}
+
+// the device address of g_featnn_fallback_rows (featnn_thresh.hip counts there too)
+int fallback_counter(unsigned long long **ctr) {
+    PCR_HIP_CHECK(hipGetSymbolAddress((void **)ctr, HIP_SYMBOL(g_featnn_fallback_rows)));
     return PCR_OK;
 }
 

@@ -148,6 +148,38 @@ __device__ __forceinline__ double bound1(double q, double ex, double G, double E
 }
 __device__ __forceinline__ double sub_term(int D) { return 6.103515625e-05 * __builtin_sqrt((double)D); }  // 2^-14 sqrt(D)
 
+// featnn_row9's certificate bound, 2 x the error of one screened value in its
+// row's frame (row_tail's kCT branch has the terms): q, ex the row's norm and
+// |x - f16(x)|, G, E the columns' maxima (ex, E with sub_term), B the pair's
+// bias, Kt the executed k
+__device__ __forceinline__ double bound_ct(double q, double ex, double G, double E, double B, int Kt) {
+    const double u = 5.9604644775390625e-08;  // 2^-24
+    const double err = 2.0 * (Kt + 2) * u * ((B + G * G) + 2.0 * (q + ex) * (G + E)) +
+                       2.0 * (ex * G + (q + ex) * E) + u * (2.0 * B + G * G) * (1.0 + 0x1p-20) + 4.0;
+    return 2.0 * err;
+}
+
+__device__ __forceinline__ unsigned umin2(unsigned a, unsigned b) { return a < b ? a : b; }
+__device__ __forceinline__ unsigned umax2(unsigned a, unsigned b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned fbits(float v) { return __float_as_uint(v); }
+
+// a lane's 16 column terms of column tile ct (register r: column
+// 8 (r / 4) + 4 h + (r % 4)), from 32 floats per tile
+__device__ __forceinline__ f32x16 colterms(const float *tile32, int h) {
+    f32x16 c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 v = *reinterpret_cast<const float4 *>(tile32 + 8 * j + 4 * h);
+        c[4 * j] = v.x; c[4 * j + 1] = v.y; c[4 * j + 2] = v.z; c[4 * j + 3] = v.w;
+    }
+    return c;
+}
+
+// featnn_thresh9 / featnn_exact_cand: candidate slots per listed row.  On the
+// C4 benchmark a failing row has 2 columns within its threshold on average and
+// 4 at most; a row with more goes to the exact rescan
+constexpr int kThreshK = 8;
+
 struct MutArgs {
     const int32_t *nn12, *n_src, *n_tgt;
     int Nmax, Mmax, mutual, ransac_n, Kt, D, ntm;
@@ -231,7 +263,72 @@ struct RowArgs5 {
     // f32(|.|^2 + B) ([P][ntc * 32], [P][ntr * 32]) and B
     const float *cct, *rct;
     const float *cbias;  // [P] B
+    // the threshold route (featnn_thresh.hip): thresh = 1 makes featnn_finish9
+    // re-mark the rows it lists as the sweep marks its own, rec = (0, B1,
+    // 0xffffffff, 1) -- featnn_thresh9's candidate counter, the row's smallest
+    // value, its first column (pass 1) and the skip flag; cand: [P][Rmax]
+    // [kThreshK] candidate columns; used: featmut's column flags (pass 2);
+    // Xc: the column cloud (f32); fbctr: g_featnn_fallback_rows; dbg:
+    // featnn_exact_cand keeps statistics
+    int thresh;
+    int *cand, *used;
+    const float *Xc;
+    unsigned long long *fbctr;
+    int dbg;
 };
+
+namespace {
+
+// The 1-term row operand of one row (lane half h) built from its f32 values:
+// its -2 f16(x) chunks exactly as the packs store them (row_frags) -- one
+// 128-byte line per row where the packed image spreads it over S lines: the
+// regroup gathers rows.  The sweep, the regroup and the threshold sweep all
+// build it here, so their MFMA chains agree bit for bit.  (No norm chunk:
+// featnn_row9 takes the columns' |y|^2 + B as the MFMA's accumulator input and
+// leaves |x|^2 out.)
+template <int S>
+__device__ __forceinline__ void row_operand1(const RowArgs5 &a, int p, int row, bool valid, int h,
+                                             f16x8 (&A)[S]) {
+    const float sc = __uint_as_float(a.sc[p]);
+    float x[16 * S];
+    const float *xr = a.Xr + ((size_t)p * a.Rmax + row) * a.D;
+    if (valid && a.D == 16 * S && ((uintptr_t)xr & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < 4 * S; ++q) {
+            const float4 v = reinterpret_cast<const float4 *>(xr)[q];
+            x[4 * q] = v.x * sc; x[4 * q + 1] = v.y * sc; x[4 * q + 2] = v.z * sc; x[4 * q + 3] = v.w * sc;
+        }
+    } else if (valid) {
+#pragma unroll
+        for (int q = 0; q < 16 * S; ++q) x[q] = q < a.D ? xr[q] * sc : 0.0f;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 16 * S; ++q) x[q] = 0.0f;
+    }
+    // both lane halves' elements at compile-time indices, then the half's pick
+    // (an index by h is a select chain over the row)
+    auto seg = [&](int k) {
+        const _Float16 hi = (_Float16)x[k];
+        return k < a.D ? (a.role == 0 ? (_Float16)(-2.0f * (float)hi) : hi) : (_Float16)0.0f;
+    };
+#pragma unroll
+    for (int c = 0; c < S; ++c)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const _Float16 v0 = seg(16 * c + j), v1 = seg(16 * c + 8 + j);
+            A[c][j] = h ? v1 : v0;
+        }
+}
+
+// the row's certificate bound (bound_ct) from a screen's arguments
+__device__ __forceinline__ double row_bound_ct(const RowArgs5 &a, int p, int row, float rexv, int Kt) {
+    const double sub = sub_term(a.D);
+    return bound_ct((double)a.rnr[(size_t)p * a.ntr * 32 + row], (double)rexv + sub,
+                    (double)__uint_as_float(a.cmax[p]), (double)__uint_as_float(a.cemax[p]) + sub,
+                    (double)a.cbias[p], Kt);
+}
+
+}  // namespace
 
 // packed operands, norms and per-pair maxima of both clouds (shared by the
 // dual screen and the mutual path)
@@ -265,5 +362,8 @@ template <bool kIdx> int launch_row7(const RowArgs5 &r, int S, hipStream_t s);  
 template <bool kIdx, bool kOne> int launch_row8(const RowArgs5 &r, int S, hipStream_t s);
 template <bool kIdx> int launch_row9(const RowArgs5 &r, int S, hipStream_t s);
 template <bool kIdx> int launch_regroup9(const RowArgs5 &r, int S, hipStream_t s);
+int fallback_counter(unsigned long long **ctr);  // g_featnn_fallback_rows's device address
+// featnn_thresh.hip: featnn_thresh9 + featnn_exact_cand over the rows r.rlist lists
+template <bool kIdx> int launch_thresh9(const RowArgs5 &r, int S, hipStream_t s);
 
 }  // namespace pcr
