@@ -27,4 +27,18 @@ PCR_THRESH_HD inline uint32_t thresh_bits_up(double t) {
     return (double)f < t ? b + 1u : b;
 }
 
+// featnn_thresh9's flush of one row's block-local hits: the block counted
+// `local` hits of the row (the first min(local, K) of them in its K local
+// slots) and `base` is what its one atomicAdd(rec.x, local) returned, the hits
+// other blocks had added before.  Returns how many local slots i = 0 .. n - 1
+// to copy to the row's global slots base + i: those that land below K, none
+// once base >= K.  The row's total is the sum of every block's `local`
+// whatever was copied, so it exceeds K exactly when the row has more than K
+// counted hits (featnn_exact_cand reads min(total, K + 1): overflow).
+PCR_THRESH_HD inline int thresh_flush_count(uint32_t base, uint32_t local, int K) {
+    if (base >= (uint32_t)K) return 0;
+    const uint32_t room = (uint32_t)K - base;
+    return (int)(local < room ? local : room);
+}
+
 }  // namespace pcr

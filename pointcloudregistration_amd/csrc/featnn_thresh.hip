@@ -20,6 +20,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include <cstdio>
+#include <type_traits>
 
 namespace pcr {
 namespace {
@@ -29,16 +30,69 @@ namespace {
 __device__ unsigned g_thresh_stat[2][3];
 
 // A block is one of a pair's column slices (steps of two column tiles, as the
-// regroup's chain); its 8 waves hold two 32-row tiles of the pair's list each
-// and walk the slice's steps together, so a step's B fragments and column
-// terms come from L2 once per block and from the CU's vector L1 for the other
-// waves (one row tile per wave, each streaming the whole image from L2 on its
-// own, measured 0.65 ms for pass 1 of C4: 1.2 GB of L2 reads per step).  The
-// hits of different slices append independently: no merge.  A pair's blocks
-// sit on one XCD (its column image in that L2).
+// regroup's chain) and walks it in rounds of W * RT = 16 row tiles of the
+// pair's list: wave w holds tiles w and w + 8 of the round, so a list of up
+// to 8 tiles has one tile on each of its waves and every SIMD has work (two
+// consecutive tiles per wave left 3 of 8 waves idle at C4's 9 tiles).
+//
+// The column stream goes through LDS as featnn_row9's: kThreshG column tiles
+// per group -- the f16 chunks by 16-byte and the column terms by 4-byte LDS
+// DMA -- double-buffered, the next group in flight while this one runs; the
+// waves read their B fragments and C terms from the group's buffer.  A slice
+// is whole steps, not whole groups: the DMA leaves out the tiles past the
+// slice's last step (the compute never reads them).
+//
+// Hits go to LDS: a counter and kThreshK slots per row of the round.  A hit
+// is one returning ds_add and a conditional ds_write (lgkmcnt), so the step
+// loop has no vector-memory instruction of its own and nothing waits on the
+// DMA in flight (one returning global atomic per hit drained it: vmcnt counts
+// in order -- DESIGN.md Round 10).  After the slice the block adds each row's
+// local count to rec.x once and copies the local slots that land below
+// kThreshK (thresh_flush_count); rec.x ends as the sum of all counted hits, as
+// before, so "more than kThreshK" still means overflow.  The hits of different
+// slices append independently: no merge.  A pair's blocks sit on one XCD (its
+// column image in that L2).
+#ifndef PCR_THRESH_G
+#define PCR_THRESH_G 16
+#endif
+#ifndef PCR_THRESH_PF
+#define PCR_THRESH_PF 1  // the next step's fragments read from LDS behind this step's MFMAs
+#endif
+constexpr int kThreshG = PCR_THRESH_G;  // column tiles per LDS group
+
+// A hit's returning LDS add and LDS store, by their LDS byte addresses.  As
+// inline asm because the compiler puts s_waitcnt vmcnt(0) in front of every
+// LDS access of its own that it cannot tie to one of the LDS DMAs in flight --
+// the hit lists are no DMA's target, so each hit would wait for the next
+// group's DMA, which is what this kernel is rid of.  Their operands are
+// addresses and column numbers, never an MFMA's accumulators (whose hazard
+// wait states the compiler does not place around inline asm).
+__device__ __forceinline__ unsigned lds_add_rtn(unsigned addr, unsigned v) {
+    unsigned r;
+    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(addr), "v"(v) : "memory");
+    return r;
+}
+__device__ __forceinline__ void lds_store(unsigned addr, int v) {
+    asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : : "v"(addr), "v"(v) : "memory");
+}
+
 template <int S, bool kIdx>
 __global__ __launch_bounds__(512) void featnn_thresh9(RowArgs5 a) {
-    constexpr int NM = 2 * S + 1, NB = S, W = 8, RT = 2;
+    constexpr int NM = 2 * S + 1, NB = S, W = 8, RT = 2, G = kThreshG, GS = G / 2;
+    constexpr int kT = G * NB * 64;     // f16x8 of a buffer's fragments
+    constexpr int kRows = W * RT * 32;  // rows of a block round: one per thread
+    static_assert(G % 2 == 0 && kRows == 512, "whole steps; the flush is one row per thread");
+    // the two buffers' fragments and column terms (G x 32 floats) as arrays of
+    // their own, each named at compile time where it is read or filled: the
+    // compiler then knows that a read of one does not touch the DMA in flight
+    // into another (behind a run-time choice of one array's parts it waits
+    // for every DMA before the reads)
+    __shared__ __attribute__((aligned(16))) f16x8 Bs0[kT];
+    __shared__ __attribute__((aligned(16))) f16x8 Bs1[kT];
+    __shared__ __attribute__((aligned(16))) float Cs0[G * 32];
+    __shared__ __attribute__((aligned(16))) float Cs1[G * 32];
+    __shared__ unsigned hcnt[kRows];
+    __shared__ int hslot[kRows * kThreshK];
     const int nbp = gridDim.x / (8 * ((a.P + 7) >> 3));  // blocks per pair
     const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3;
     const int p = (slot / nbp) * 8 + xcd, sl = slot % nbp;
@@ -47,31 +101,63 @@ __global__ __launch_bounds__(512) void featnn_thresh9(RowArgs5 a) {
     const int m = count_of(a.n_cols, p, a.Cmax);
     const int nst = (((m + 31) >> 5) + 1) >> 1;  // column steps (2 nst <= ntc: ntc is even)
     const int nsl = min(nbp, nst);
-    if (nr <= 0 || sl >= nsl) return;
+    if (nr <= 0 || sl >= nsl) return;  // whole block
     const int s0 = (int)((long long)nst * sl / nsl), s1 = (int)((long long)nst * (sl + 1) / nsl);
+    const int ngr = (s1 - s0 + GS - 1) / GS;  // the slice's groups, the last one short
     const int wid = threadIdx.x >> 6, l = threadIdx.x & 63, h = l >> 5;
     const int ntl = (nr + 31) >> 5;
     const int *rl = a.rlist + (size_t)p * a.Rmax;
     const f16x8 *bimg = a.Bp + (size_t)p * a.ntc * NM * 64 + l;
-    const float *ctp = a.cct + (size_t)p * a.ntc * 32;
-    auto load = [&](int st, f16x8 (&Bf)[2][NB], f32x16 (&Cf)[2]) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-#pragma unroll
-            for (int c = 0; c < NB; ++c) Bf[u][c] = bimg[((size_t)(2 * st + u) * NM + c) * 64];
-            Cf[u] = colterms(ctp + (size_t)(2 * st + u) * 32, h);
+    const float *ctp = a.cct + (size_t)p * a.ntc * 32 + l;
+    // group grp of the slice into buffer bufi: tiles [2 sg, 2 min(sg + GS, s1))
+    // (all below 2 nst <= ntc: inside the pair's image and terms)
+    auto issue = [&](auto bufc_, int grp) {
+        f16x8 *Bs = decltype(bufc_)::value ? Bs1 : Bs0;
+        float *Cs = decltype(bufc_)::value ? Cs1 : Cs0;
+        const int sg = s0 + grp * GS;
+        for (int c = wid; c < G * NB + GS; c += W) {
+            if (c >= G * NB) {  // a step's column terms: two tiles, 4 B per lane
+                const int j = c - G * NB;
+                if (sg + j < s1)
+                    __builtin_amdgcn_global_load_lds(
+                        (const __attribute__((address_space(1))) void *)(ctp + (size_t)(sg + j) * 64),
+                        (__attribute__((address_space(3))) void *)(Cs + j * 64),
+                        4, 0, 0);
+                continue;
+            }
+            const int g = c / NB, cc = c - g * NB;
+            if (sg + (g >> 1) < s1)
+                __builtin_amdgcn_global_load_lds(
+                    (const __attribute__((address_space(1))) void *)(bimg + ((size_t)(2 * sg + g) * NM + cc) * 64),
+                    (__attribute__((address_space(3))) void *)(Bs + c * 64), 16, 0, 0);
         }
     };
-    // the wave's row tiles t0, t0 + 1 (a list past 16 tiles: the next 16, ...)
-    for (int t0 = wid * RT; t0 < ntl; t0 += W * RT) {
+    // min of a lane's values x[8 q .. 8 q + 7] of one column tile (featnn_row9's chains)
+    auto min8 = [](const f32x16 &x, int q) {
+        unsigned c = umin2(umin2(fbits(x[8 * q]), fbits(x[8 * q + 1])), fbits(x[8 * q + 2]));
+        c = umin2(umin2(c, fbits(x[8 * q + 3])), fbits(x[8 * q + 4]));
+        c = umin2(umin2(c, fbits(x[8 * q + 5])), fbits(x[8 * q + 6]));
+        return umin2(c, fbits(x[8 * q + 7]));
+    };
+    for (int tb = 0; tb < ntl; tb += W * RT) {
+        // (the previous round's flush is behind a barrier; the hits of this one
+        // come after the first group's)
+        hcnt[threadIdx.x] = 0u;
+        issue(std::integral_constant<int, 0>{}, 0);
+        // the wave's row tiles tb + wid and tb + wid + 8
+        const int nt = tb + wid + W < ntl ? 2 : (tb + wid < ntl ? 1 : 0);
         size_t o[RT];
         unsigned B1[RT], thr[RT], am[RT];
         bool live[RT];
-        int nh[RT];
+        int nh[RT], lr[RT];
+        unsigned ca[RT], sa[RT];  // the LDS addresses of the row's counter and slots
         f16x8 A[RT][NB];
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
-            const int k = (t0 + t) * 32 + (l & 31);
+            lr[t] = (t * W + wid) * 32 + (l & 31);  // the row's slot of the round
+            ca[t] = (unsigned)(uintptr_t)(hcnt + lr[t]);
+            sa[t] = (unsigned)(uintptr_t)(hslot + lr[t] * kThreshK);
+            const int k = tb * 32 + lr[t];
             const bool valid = k < nr;
             const int row = valid ? rl[k] : 0;
             o[t] = (size_t)p * a.Rmax + row;
@@ -89,64 +175,109 @@ __global__ __launch_bounds__(512) void featnn_thresh9(RowArgs5 a) {
             am[t] = 0xffffffffu;  // pass 1: the first column whose value is B1
             nh[t] = 0;            // this lane's hits in this slice
         }
-        f16x8 Bf[2][NB];
-        f32x16 Cf[2];
-        load(s0, Bf, Cf);
-        for (int st = s0; st < s1; ++st) {
-            f16x8 Bn[2][NB];
-            f32x16 Cn[2];
-            // the next step's, in flight behind this one's MFMAs (two steps
-            // ahead, 48 more VGPRs at the same two waves per SIMD, measured
-            // slower: pass 2 0.30 against 0.16 ms)
-            load(st + 1 < s1 ? st + 1 : st, Bn, Cn);
-            f32x16 acc[RT][2];
-#pragma unroll
-            for (int c = 0; c < NB; ++c)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int t = 0; t < RT; ++t)
-                        acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bf[u][c], A[t][c],
-                                                                           c == 0 ? Cf[u] : acc[t][u], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < RT; ++t)
+        // one group of the slice for the wave's NT row tiles
+        auto sweep = [&](auto ntc_, auto bufc_, int grp) {
+            constexpr int NT = decltype(ntc_)::value;
+            const f16x8 *Bs = decltype(bufc_)::value ? Bs1 : Bs0;
+            const float *Cb = decltype(bufc_)::value ? Cs1 : Cs0;
+            const int sg = s0 + grp * GS, ns = min(GS, s1 - sg);
+            const f16x8 *Bb = Bs + l;
+            auto load = [&](int j, f16x8 (&Bf)[2][NB], f32x16 (&Cf)[2]) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
-                    // one compare per value, its wave mask OR-ed on the scalar
-                    // side; a dead lane's threshold pattern is 0, below every
-                    // value.  A wave's 32 rows have ~64 hits in 256 column
-                    // tiles: three tiles of four skip the scan below (a scan
-                    // of a step's 32 values whenever any was a hit ran on
-                    // nearly every step: 0.31 ms for pass 1 of C4)
-                    unsigned long long any = 0ull;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) any |= __ballot(fbits(acc[t][u][r]) <= thr[t]);
-                    if (any == 0ull) continue;
+                    for (int c = 0; c < NB; ++c) Bf[u][c] = Bb[((2 * j + u) * NB + c) * 64];
+                    Cf[u] = colterms(Cb + (2 * j + u) * 32, h);
+                }
+            };
+            f16x8 Bf[2][NB];
+            f32x16 Cf[2];
+            if (PCR_THRESH_PF) load(0, Bf, Cf);
+            for (int j = 0; j < ns; ++j) {
+                const int st = sg + j;
+                f16x8 Bn[2][NB];
+                f32x16 Cn[2];
+                if (PCR_THRESH_PF) load(j + 1 < ns ? j + 1 : j, Bn, Cn);
+                else load(j, Bf, Cf);
+                f32x16 acc[NT][2];
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const unsigned v = fbits(acc[t][u][r]);
-                        const int col = 32 * (2 * st + u) + 8 * (r >> 2) + 4 * h + (r & 3);
-                        if (v <= thr[t] && live[t] && col < m) {
-                            if (kIdx && v == B1[t]) am[t] = umin2(am[t], (unsigned)col);
-                            // past kThreshK + 1 hits of its own the lane stops counting: the row overflows
-                            if (nh[t] <= kThreshK) {
-                                const unsigned pos = atomicAdd(reinterpret_cast<unsigned *>(a.rec + o[t]), 1u);
-                                if (pos < (unsigned)kThreshK) a.cand[o[t] * kThreshK + pos] = col;
+                for (int c = 0; c < NB; ++c)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u)
+#pragma unroll
+                        for (int t = 0; t < NT; ++t)
+                            acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bf[u][c], A[t][c],
+                                                                               c == 0 ? Cf[u] : acc[t][u], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        // one compare of the lane's smallest value against the
+                        // row's threshold; a dead lane's pattern is 0, below
+                        // every value.  A wave's 32 rows have ~64 hits in 256
+                        // column tiles: three tiles of four skip the scan, and
+                        // the others scan the half of the registers with the hit
+                        const unsigned m0 = min8(acc[t][u], 0), m1 = min8(acc[t][u], 1);
+                        if (__ballot(umin2(m0, m1) <= thr[t]) == 0ull) continue;
+                        const bool half[2] = {__ballot(m0 <= thr[t]) != 0ull, __ballot(m1 <= thr[t]) != 0ull};
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            if (!half[r >> 3]) continue;
+                            const unsigned v = fbits(acc[t][u][r]);
+                            const int col = 32 * (2 * st + u) + 8 * (r >> 2) + 4 * h + (r & 3);
+                            if (v <= thr[t] && live[t] && col < m) {
+                                if (kIdx && v == B1[t]) am[t] = umin2(am[t], (unsigned)col);
+                                // past kThreshK + 1 hits of its own the lane stops counting: the row overflows
+                                if (nh[t] <= kThreshK) {
+                                    const unsigned pos = lds_add_rtn(ca[t], 1u);
+                                    if (pos < (unsigned)kThreshK) lds_store(sa[t] + 4u * pos, col);
+                                }
+                                ++nh[t];
                             }
-                            ++nh[t];
                         }
                     }
+                if (PCR_THRESH_PF) {
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+                        for (int c = 0; c < NB; ++c) Bf[u][c] = Bn[u][c];
+                        Cf[u] = Cn[u];
+                    }
                 }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-#pragma unroll
-                for (int c = 0; c < NB; ++c) Bf[u][c] = Bn[u][c];
-                Cf[u] = Cn[u];
             }
+        };
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        auto group = [&](auto bufc_, int grp) {
+            constexpr int buf = decltype(bufc_)::value;
+            if (grp + 1 < ngr) issue(std::integral_constant<int, buf ^ 1>{}, grp + 1);
+            if (nt == 2) sweep(std::integral_constant<int, 2>{}, bufc_, grp);
+            else if (nt == 1) sweep(std::integral_constant<int, 1>{}, bufc_, grp);
+            // the next group's DMA has landed for every wave, and every wave is done
+            // reading this buffer before the group after next overwrites it
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        };
+        for (int grp = 0; grp < ngr; grp += 2) {
+            group(std::integral_constant<int, 0>{}, grp);
+            if (grp + 1 < ngr) group(std::integral_constant<int, 1>{}, grp + 1);
         }
 #pragma unroll
         for (int t = 0; t < RT; ++t)
             if (kIdx && am[t] != 0xffffffffu) atomicMin(reinterpret_cast<unsigned *>(a.rec + o[t]) + 2, am[t]);
+        // the flush (every wave's hits are behind the last group's barrier):
+        // thread r takes row slot r of the round
+        {
+            const int r = threadIdx.x, k = tb * 32 + r;
+            const unsigned lc = hcnt[r];
+            if (k < nr && lc != 0u) {
+                const size_t oo = (size_t)p * a.Rmax + rl[k];
+                const unsigned base = atomicAdd(reinterpret_cast<unsigned *>(a.rec + oo), lc);
+                const int n = thresh_flush_count(base, lc, kThreshK);
+                for (int i = 0; i < n; ++i) a.cand[oo * kThreshK + base + i] = hslot[r * kThreshK + i];
+            }
+        }
+        __syncthreads();  // the next round clears the counters
     }
 }
 
@@ -255,16 +386,16 @@ __global__ __launch_bounds__(256) void featnn_exact_cand(RowArgs5 a) {
 
 }  // namespace
 
-// blocks (column slices) per pair of featnn_thresh9: ~1024 blocks whatever the
-// batch -- 4 slices at 256 pairs, 32 at 32 pairs and below (PCR_THRESH_SLICES:
-// A/B, DESIGN.md Round 9 has the measurements)
+// blocks (column slices) per pair of featnn_thresh9: ~256 blocks whatever the
+// batch, one per CU -- 1 slice at 256 pairs, 8 at 32 pairs, 32 at 8 pairs and
+// below (PCR_THRESH_SLICES: A/B, DESIGN.md Round 10 has the measurements)
 static int thresh_blocks_per_pair(int P) {
     static const int forced = [] {
         const char *e = getenv("PCR_THRESH_SLICES");
         return e ? atoi(e) : 0;
     }();
     if (forced >= 1 && forced <= 128) return forced;
-    return std::max(4, std::min(32, 1024 / std::max(P, 1)));
+    return std::max(1, std::min(32, 256 / std::max(P, 1)));
 }
 
 template <bool kIdx>
