@@ -78,6 +78,15 @@ int pcr_featnn_rescan_rows(int64_t *rows12, int64_t *rows21, int32_t reset);
  * 1-term f16 feature screens could not certify and left to the 3-term split
  * screen since the last reset.  Synchronizes the device. */
 int pcr_featnn_fallback_rows(int64_t *rows12, int64_t *cols21, int32_t reset);
+/* Diagnostic: the chunks (16 f16 of every row) per 32-row tile that the last
+ * f16 split-screen prepare stored in its packed operand images.  With S =
+ * ceil(D / 16): S on the default route of pcr_feature_correspondences at D <=
+ * 32 (the compact image: the hi halves only, all that featnn_row9 and the
+ * threshold route read), 2 S + 1 (hi | lo | norms) for pcr_feature_match, D >
+ * 32, the PCR_FEAT_THRESH=0 / PCR_FEAT_ROW9=0 / PCR_FEAT_ONE=0 routes, and
+ * with PCR_FEAT_IMAGE=full (read per call: the full image on the default
+ * route, same results).  0 before the first prepare. */
+int pcr_featnn_image_chunks(int32_t *chunks);
 /* diagnostic: copy `bytes` of pcr_feature_correspondences' scratch from its
  * last call (device to device, on `stream`) */
 int pcr_featmut_debug_copy(void *dst, int64_t bytes, pcr_stream_t stream);

@@ -142,6 +142,8 @@ def load():
         lib.pcr_featnn_rescan_rows.argtypes = [ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32]
         lib.pcr_featnn_fallback_rows.restype = ctypes.c_int
         lib.pcr_featnn_fallback_rows.argtypes = [ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32]
+        lib.pcr_featnn_image_chunks.restype = ctypes.c_int
+        lib.pcr_featnn_image_chunks.argtypes = [ctypes.POINTER(_i32)]
         lib.pcr_ndp_train_partial_floats.restype = _i64
         lib.pcr_ndp_train_partial_floats.argtypes = [_i32, _i32, _i32, _i32]
         lib.pcr_ndp_chamfer_scratch_bytes.restype = _i64
@@ -172,7 +174,7 @@ def load():
 
 def exported_symbols():
     return ["pcr_last_error", "pcr_version", "pcr_workspace_release", "pcr_profile_enable", "pcr_profile_read",
-            "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_ndp_train_partial_floats", "pcr_ndp_chamfer_scratch_bytes",
+            "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_featnn_image_chunks", "pcr_ndp_train_partial_floats", "pcr_ndp_chamfer_scratch_bytes",
             "pcr_ndp_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words", "pcr_ndp_chamfer_max_points",
             "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_shutdown"] + \
         list(SIGNATURES)
@@ -236,6 +238,17 @@ def featnn_fallback_rows(reset=True):
     if rc != PCR_OK:
         raise PcrError(load().pcr_last_error().decode())
     return a.value, b.value
+
+
+def featnn_image_chunks():
+    """Chunks per tile of the last f16 feature screen's packed images: S =
+    ceil(D / 16) for the compact image of the default correspondence route, 2 S + 1
+    for the full one (every other route; PCR_FEAT_IMAGE=full forces it)."""
+    c = _i32(0)
+    rc = load().pcr_featnn_image_chunks(ctypes.byref(c))
+    if rc != PCR_OK:
+        raise PcrError(load().pcr_last_error().decode())
+    return c.value
 
 
 def call(name, *args):

@@ -29,6 +29,7 @@
 #include "featnn_v5.h"
 #include "scan.h"
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 
 namespace pcr {
@@ -257,6 +258,13 @@ static bool feat_thresh() {
     return !(e && e[0] == '0');
 }
 
+// PCR_FEAT_IMAGE=full: the full 2S + 1 chunk image on the default route too
+// (A/B, the parity tests; read per call)
+static bool feat_image_full() {
+    const char *e = getenv("PCR_FEAT_IMAGE");
+    return e && strcmp(e, "full") == 0;
+}
+
 // the 1-term screens in front of the 3-term ones (S <= 2): on by default,
 // PCR_FEAT_ONE=0 for the round-5 path (A/B, the parity tests; read per call)
 static bool feat_one_term() {
@@ -345,10 +353,22 @@ static RowArgs5 fallback_args(RowArgs5 r, int *list, int *count, int fbdiag, int
 static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
                              const int32_t *n_src, const int32_t *n_tgt, int mutual, int ransac_n,
                              int32_t *nn12, int32_t *corres, int32_t *n_corres, hipStream_t s) {
+    // The route, ahead of the prepare (it decides the images' layout): from S,
+    // the tile counts as v5_prepare pads them, and the hooks.
+    const int S0 = cdiv(D, 16), rg = std::max(kRow8G, kRow9G);
+    const int ntn0 = cdiv(cdiv(Nmax, 32), 16) * 16, ntm0 = cdiv(cdiv(Mmax, 32), rg) * rg;
+    const bool one = S0 <= 2 && feat_one_term();
+    // (the regroup keeps a pair's per-step prefix in LDS)
+    const bool use9 = one && feat_row9() && std::max(ntm0, ntn0) / 2 <= kRegroupMaxSteps;
+    const bool thresh = use9 && feat_thresh();
+    // featnn_row9 with the threshold route reads the images' hi segment only:
+    // the compact image (S chunks per tile); every other route reads lo / norms
+    const bool compact = thresh && !feat_image_full();
     V5Buf v;
-    int rc = v5_prepare(F, G, P, Nmax, Mmax, D, n_src, n_tgt, s, v);
+    int rc = v5_prepare(F, G, P, Nmax, Mmax, D, n_src, n_tgt, s, v, compact);
     if (rc != PCR_OK) return rc;
     const int ntn = v.ntn, ntm = v.ntm;
+    PCR_REQUIRE(v.S == S0 && ntn == ntn0 && ntm == ntm0, PCR_ERR_ARG, "feature_corres: tile counts");
     // scratch: v12 [P][Nmax] f64 | e12 [P][Nmax] f32 | wq [P][Mmax] float4 | used, pos
     // [P][Mmax+1] | jlist, nn21x [P][Mmax] | flag [P][Nmax+1] | nj, zero [P] | nns [P][Nmax]
     const size_t pn = (size_t)P * Nmax, pm = (size_t)P * Mmax;
@@ -361,10 +381,6 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
     const size_t pr = (size_t)P * std::max(Nmax, Mmax);
     const int fsl = list_slices(P);
     const size_t pt = fsl > 1 ? (size_t)fsl * pr : 0;  // the sliced 3-term screens' partials
-    const bool one = v.S <= 2 && feat_one_term();
-    // (the regroup keeps a pair's per-step prefix in LDS)
-    const bool use9 = one && feat_row9() && std::max(ntm, ntn) / 2 <= kRegroupMaxSteps;
-    const bool thresh = use9 && feat_thresh();
     MutArgs ma;
     double *v12;
     float *e12;
@@ -406,7 +422,7 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
     ma.corres = corres; ma.n_corres = n_corres;
     // pass 1: F rows x all G columns (nrb: each launcher sets its own)
     RowArgs5 r;
-    r.Ap = v.Ap; r.Bp = v.Bp; r.rnr = v.fnr; r.cmax = v.gmax; r.n_rows = n_src; r.n_cols = n_tgt;
+    r.Ap = v.Ap; r.Bp = v.Bp; r.ich = v.ich; r.rnr = v.fnr; r.cmax = v.gmax; r.n_rows = n_src; r.n_cols = n_tgt;
     r.rlist = nullptr; r.rcount = nullptr; r.P = P; r.Rmax = Nmax; r.Cmax = Mmax; r.ntr = ntn;
     r.ntc = ntm; r.nrb = 0; r.D = D; r.ctbits = 1;
     while ((1 << r.ctbits) < ntm) ++r.ctbits;

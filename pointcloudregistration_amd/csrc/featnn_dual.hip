@@ -266,6 +266,7 @@ int feature_match_v5(const float *F, const float *G, int P, int Nmax, int Mmax, 
     V5Buf v;
     int rc = v5_prepare(F, G, P, Nmax, Mmax, D, n_src, n_tgt, s, v);
     if (rc != PCR_OK) return rc;
+    PCR_REQUIRE(v.ich == v.NM, PCR_ERR_ARG, "feature_match: the dual screen needs the full operand image");
     const int W = v.W, nrb = v.nrb, ntm = v.ntm;
     DualArgs5 d;
     d.Ap = v.Ap; d.Bp = v.Bp; d.fnr = v.fnr; d.gnr = v.gnr; d.fmax = v.fmax; d.gmax = v.gmax;

@@ -169,8 +169,10 @@ __device__ __forceinline__ void pack_pairs(const PackCtl &c, int T, Body body) {
 
 // role 0: rows (A), role 1: columns (B).  256-thread blocks, one wave per
 // 32-row tile; each tile is staged through LDS with coalesced loads (scaled,
-// exact) and every lane emits its 2S + 1 stored 16-byte operand fragments.
-__global__ __launch_bounds__(256) void feat_pack5(PackIO io, int D, int S, Split5 sp, PackCtl pc) {
+// exact) and every lane emits its stored 16-byte operand fragments: NS = 2S + 1
+// chunks per tile, or NS = S (compact: the hi segment alone, the same bits; the
+// lo halves, the norm parts and c are then not computed).
+__global__ __launch_bounds__(256) void feat_pack5(PackIO io, int D, int S, int NS, Split5 sp, PackCtl pc) {
     const int role = blockIdx.z;
     const float *X = io.X[role];
     const int32_t *n = io.n[role];
@@ -210,8 +212,10 @@ __global__ __launch_bounds__(256) void feat_pack5(PackIO io, int D, int S, Split
             ea = ea + e * e;
         }
         // norm parts of acc / c (exact power-of-two division)
-        _Float16 np[3];
-        if (valid) {
+        _Float16 np[3] = {(_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f};
+        if (NS == S) {
+            // compact: no norm chunk
+        } else if (valid) {
             double wv = acc * __builtin_ldexp(1.0, -sp.cs);
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
@@ -226,9 +230,8 @@ __global__ __launch_bounds__(256) void feat_pack5(PackIO io, int D, int S, Split
             np[2] = (_Float16)65504.0f;
         }
         const _Float16 cval = (_Float16)__builtin_ldexpf(1.0f, sp.cs);
-        const int NM = 2 * S + 1;
-        f16x8 *dst = Xp + ((size_t)p * ntiles + t) * NM * 64 + l;
-        for (int c = 0; c < NM; ++c) {
+        f16x8 *dst = Xp + ((size_t)p * ntiles + t) * NS * 64 + l;
+        for (int c = 0; c < NS; ++c) {
             f16x8 o;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -387,6 +390,86 @@ __global__ __launch_bounds__(256) void feat_pack5r(PackIO io, Split5 sp, PackCtl
     });
 }
 
+// The compact image's register-resident pack (round 11): the hi segment alone,
+// S chunks per tile.  Without the lo and norm chunks a lane half has nothing of
+// its own left to compute, and feat_pack5r's second half would only repeat the
+// first one's row (the loads, the f64 sums, the conversions: the kernel is
+// VALU-issue bound once its dead stores are gone).  So here a lane is ONE row
+// and a wave two tiles (lane l: tile 2 w + l / 32, row l % 32): the row is
+// loaded, scaled, checked and summed once, and the lane stores all 2 S
+// fragments of its row -- per store the wave's halves write 512 contiguous
+// bytes of their two tiles.  Same values as feat_pack5r's: the same operations
+// in the same order per row (x s, the f64 sums over k ascending, f16(x s), -2 x
+// for the row role), the same per-row arrays and per-pair maxima.
+template <int D>
+__global__ __launch_bounds__(256) void feat_pack5c(PackIO io, Split5 sp, PackCtl pc) {
+    static_assert(D % 16 == 0, "whole chunks (no zero tail), float4 rows");
+    const int role = blockIdx.z;
+    const float *X = io.X[role];
+    const int32_t *n = io.n[role];
+    const int Nmax = io.Nmax[role], ntiles = io.ntiles[role];
+    f16x8 *Xp = io.Xp[role];
+    float *nrm = io.nrm[role];
+    unsigned *nmax = io.nmax[role];
+    if ((int)blockIdx.x * 8 >= ntiles) return;  // whole block: the other cloud has more tiles
+    constexpr int S = D / 16;  // stored chunks
+    __shared__ unsigned wmax[4];
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int t = blockIdx.x * 8 + 2 * w + (l >> 5);  // ntiles is a multiple of 8 (host pads)
+    const int rr = l & 31;
+    const float lim = __builtin_ldexpf(1.0f, sp.T);
+    pack_pairs(pc, sp.T, [&](int p, float s, bool check) {
+        const int cnt = count_of(n, p, Nmax);
+        const bool valid = t * 32 + rr < cnt;
+        float x[D];
+        if (valid) {
+            const float4 *row = reinterpret_cast<const float4 *>(X + ((size_t)p * Nmax + (size_t)t * 32 + rr) * D);
+#pragma unroll
+            for (int q = 0; q < D / 4; ++q) {
+                const float4 v = row[q];
+                x[4 * q] = v.x * s; x[4 * q + 1] = v.y * s; x[4 * q + 2] = v.z * s; x[4 * q + 3] = v.w * s;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < D; ++k) x[k] = 0.0f;
+        }
+        if (check) {
+            bool ok = true;
+#pragma unroll
+            for (int k = 0; k < D; ++k) ok = ok && __builtin_fabsf(x[k]) < lim;  // NaN / inf: not ok
+            if (!ok) pc.bad[p] = 1;
+        }
+        double acc = 0.0, ea = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const double v = (double)x[k];
+            acc = acc + v * v;
+            const double e = (double)(x[k] - (float)(_Float16)x[k]);  // exact in f32
+            ea = ea + e * e;
+        }
+        f16x8 *dst = Xp + ((size_t)p * ntiles + t) * S * 64 + rr;
+#pragma unroll
+        for (int g = 0; g < 2 * S; ++g) {  // fragment g: chunk g / 2, lane half g % 2
+            f16x8 o;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const _Float16 hi = (_Float16)x[8 * g + j];
+                o[j] = role == 0 ? (_Float16)(-2.0f * (float)hi) : hi;
+            }
+            dst[(size_t)(g >> 1) * 64 + 32 * (g & 1)] = o;
+        }
+        // the pair's maxima: one atomic per WORKGROUP (see feat_pack5)
+        const float r = valid ? (float)__builtin_sqrt(acc) : 0.0f;
+        const size_t ro = (size_t)p * ntiles * 32 + t * 32 + rr;
+        nrm[ro] = r;
+        io.rex[role][ro] = valid ? split_err_norm(ea) : 0.0f;
+        io.ct[role][ro] = valid ? (float)acc : -1.0f;
+        block_max_atomic(__float_as_uint(r), wmax, nmax + p);
+        __syncthreads();
+        block_max_atomic(valid ? __float_as_uint(split_err_norm(ea)) : 0u, wmax, io.emax[role] + p);
+    });
+}
+
 // featnn_row9's column terms (after the packs and their repairs): the packs
 // stored f32(|x s|^2) per row, -1 on padding rows; here ct = f32(that + B), B the
 // pair's bias.  The sweep, the regroup and the finish order the screened values
@@ -438,12 +521,17 @@ __global__ __launch_bounds__(256) void feat_colterms(float *fct, float *gct, int
     *ct = x < 0.0f ? (float)(16.0 * B) : (float)((double)x + B);
 }
 
+// chunks per tile of the last prepare's images (diagnostic, pcr_featnn_image_chunks)
+int g_image_chunks = 0;
+
 }  // namespace
 
 int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D, const int32_t *n_src,
-               const int32_t *n_tgt, hipStream_t s, V5Buf &v) {
+               const int32_t *n_tgt, hipStream_t s, V5Buf &v, bool compact) {
     v.S = cdiv(D, 16);
     v.NM = 2 * v.S + 1;
+    v.ich = compact ? v.S : v.NM;
+    g_image_chunks = v.ich;
     v.NX = 3 * v.S + 1;
     v.sp = split5_params(D);
     v.W = 8;                                          // waves (32-row tiles) per workgroup
@@ -455,8 +543,8 @@ int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
     v.ctbits = 1;
     while ((1 << v.ctbits) < std::max(v.ntm, v.ntn)) ++v.ctbits;
     PCR_REQUIRE(v.ctbits <= 16, PCR_ERR_ARG, "feature_match: N=%d / M=%d too large", Nmax, Mmax);
-    const int NM = v.NM, ntn = v.ntn, ntm = v.ntm;
-    const size_t ap = (size_t)P * ntn * NM * 64, bp = (size_t)P * ntm * NM * 64;  // f16x8
+    const int ich = v.ich, ntn = v.ntn, ntm = v.ntm;
+    const size_t ap = (size_t)P * ntn * ich * 64, bp = (size_t)P * ntm * ich * 64;  // f16x8
     const size_t nn_n = (size_t)P * ntn * 32, nn_m = (size_t)P * ntm * 32;
     const size_t pn = (size_t)P * Nmax, pm = (size_t)P * Mmax;
     unsigned *mxp, *smax;
@@ -497,8 +585,12 @@ int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
         PackIO io{{F, G}, {n_src, n_tgt}, {Nmax, Mmax}, {ntn, ntm}, {v.Ap, v.Bp}, {v.fnr, v.gnr}, {v.fmax, v.gmax},
                   {v.femax, v.gemax}, {v.fre, v.gre}, {v.fct, v.gct}};
         const dim3 grid(cdiv(std::max(ntn, ntm), 4), gy, 2);
-        if (D == 32) hipLaunchKernelGGL(feat_pack5r<32>, grid, dim3(256), 0, s, io, v.sp, pc);  // register-resident
-        else hipLaunchKernelGGL(feat_pack5, grid, dim3(256), 0, s, io, D, v.S, v.sp, pc);
+        // (the repair launch stores the layout of the first)
+        static_assert(kRow8G % 8 == 0, "feat_pack5c: whole blocks of eight tiles");
+        if (D == 32 && compact)  // a row per lane, eight tiles per block (ntn: a multiple of 16, ntm: of kRow8G)
+            hipLaunchKernelGGL(feat_pack5c<32>, dim3(cdiv(std::max(ntn, ntm), 8), gy, 2), dim3(256), 0, s, io, v.sp, pc);
+        else if (D == 32) hipLaunchKernelGGL(feat_pack5r<32>, grid, dim3(256), 0, s, io, v.sp, pc);  // register-resident
+        else hipLaunchKernelGGL(feat_pack5, grid, dim3(256), 0, s, io, D, v.S, ich, v.sp, pc);
         PCR_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(feat_colterms, dim3(cdiv(std::max(ntn, ntm) * 32, 256), P, 2), dim3(256), 0, s, v.fct, v.gct,
@@ -509,3 +601,10 @@ int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
 }
 
 }  // namespace pcr
+
+extern "C" int pcr_featnn_image_chunks(int32_t *chunks) {
+    pcr::clear_error();
+    PCR_REQUIRE(chunks, PCR_ERR_ARG, "featnn_image_chunks: null pointer");
+    *chunks = pcr::g_image_chunks;
+    return PCR_OK;
+}

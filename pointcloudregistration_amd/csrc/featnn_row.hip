@@ -788,8 +788,7 @@ __device__ __forceinline__ unsigned group_min32(const f32x16 &x, const f32x16 &y
 template <int S, int G, bool kIdx>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void featnn_row9(RowArgs5 a) {
     constexpr int W = 8, RT = 2;          // waves per workgroup, row tiles per wave
-    constexpr int NM = 2 * S + 1;         // stored k-chunks of the packed images
-    constexpr int NB = S;                 // executed chunks: the f16 segment
+    constexpr int NB = S;                 // executed chunks: the f16 segment (a tile's first NB of a.ich stored)
     constexpr int kT = G * NB * 64;       // f16x8 of a B buffer's fragments
     constexpr int kB = kT + G * 8;        // + the group's column terms (G x 32 floats)
     static_assert(G % 8 == 0 && S <= 2, "column tiles in pairs; the terms in whole 1 KB DMA pieces");
@@ -812,14 +811,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void f
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
         const int k = (qt0 + t) * 32 + (l & 31);
-        row_operand1<S>(a, p, rl ? (k < nr ? rl[k] : 0) : k, k < nr, h, A[t]);
+        row_operand<S, kIdx ? 0 : 1>(a, p, rl ? (k < nr ? rl[k] : 0) : (k < nr ? k : 0), k < nr, h, A[t]);
     }
     // per row tile: B1, B2, I as above; pm the min of the current step's
     // first column tile (the group's first half)
     unsigned B1[RT], B2[RT], I[RT], pm[RT];
 #pragma unroll
     for (int t = 0; t < RT; ++t) { B1[t] = 0x7f800000u; B2[t] = 0x7f800000u; I[t] = 0u; pm[t] = 0x7f800000u; }
-    const f16x8 *bsrc = a.Bp + (size_t)p * a.ntc * NM * 64 + l;
+    const int nm = a.ich;  // the image's tile stride in chunks
+    const f16x8 *bsrc = a.Bp + (size_t)p * a.ntc * nm * 64 + l;
     const float *csrc = a.cct + (size_t)p * a.ntc * 32 + 4 * l;
     auto issue = [&](int grp, int bufi) {
         for (int c = wid; c < G * NB + kTC; c += W) {
@@ -831,7 +831,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void f
                 continue;
             }
             const int g = c / NB, cc = c - g * NB;
-            const f16x8 *src = bsrc + ((size_t)(grp * G + g) * NM + cc) * 64;
+            const f16x8 *src = bsrc + ((size_t)(grp * G + g) * nm + cc) * 64;
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) void *)src,
                 (__attribute__((address_space(3))) void *)(Bs + bufi * kB + c * 64), 16, 0, 0);
@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void f
 // rows per workgroup and the registers it kept live.)
 template <int S, bool kIdx>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void featnn_regroup9(RowArgs5 a) {
-    constexpr int NM = 2 * S + 1, NB = S;
+    constexpr int NB = S;
     // the pair's per-step tile prefix and row counts, 2 (steps + 1) ints of
     // dynamic LDS (a static 4097-entry pair held 32 KB and four blocks per CU)
     extern __shared__ int rg_lds[];
@@ -1057,7 +1057,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
     if (t == 0) ts[nst] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     __syncthreads();
     const int ntiles = ts[nst];
-    const f16x8 *bimg = a.Bp + (size_t)p * a.ntc * NM * 64 + l;
+    const int nm = a.ich;  // the image's tile stride in chunks
+    const f16x8 *bimg = a.Bp + (size_t)p * a.ntc * nm * 64 + l;
     const float *ctp = a.cct + (size_t)p * a.ntc * 32;
     const uint4 *bl = a.blist + (size_t)p * nst * a.bcap;
     // tile q's bucket, its rows' entries (the next tile's loaded while this one runs)
@@ -1089,11 +1090,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
 #pragma unroll
-            for (int c = 0; c < NB; ++c) Bf[u][c] = bimg[((size_t)(2 * b + u) * NM + c) * 64];
+            for (int c = 0; c < NB; ++c) Bf[u][c] = bimg[((size_t)(2 * b + u) * nm + c) * 64];
             acc[u] = colterms(ctp + (size_t)(2 * b + u) * 32, h);
         }
         f16x8 A[NB];
-        row_operand1<S>(a, p, row, valid, h, A);
+        row_operand<S, 2>(a, p, row, valid, h, A);
 #pragma unroll
         for (int c = 0; c < NB; ++c)
 #pragma unroll
@@ -1196,6 +1197,7 @@ constexpr int kRow7RT = 1, kRow7G = 4;
 template <bool kIdx>
 int launch_row7(const RowArgs5 &r0, int S, hipStream_t s) {
     RowArgs5 r = r0;
+    PCR_REQUIRE(r.ich == 2 * S + 1, PCR_ERR_ARG, "featnn_row7: needs the full operand image (%d chunks)", r.ich);
     r.nrb = cdiv(cdiv(r.Rmax, 32), 8 * kRow7RT);  // 8 waves x 1 row tile per workgroup
     const long long nblk = 8LL * r.nrb * cdiv(r.P, 8);  // XCD-aware 1-D grid
     PCR_REQUIRE(nblk < (1LL << 31), PCR_ERR_ARG, "feature_match: grid too large");
@@ -1212,6 +1214,7 @@ int launch_row7(const RowArgs5 &r0, int S, hipStream_t s) {
 template <bool kIdx, bool kOne>
 int launch_row8(const RowArgs5 &r0, int S, hipStream_t s) {
     RowArgs5 r = r0;
+    PCR_REQUIRE(r.ich == 2 * S + 1, PCR_ERR_ARG, "featnn_row8: needs the full operand image (%d chunks)", r.ich);
     r.nrb = cdiv(cdiv(r.Rmax, 32), 8 * 2);  // 8 waves x 2 row tiles per workgroup
     const int csl = r.rbmajor ? r.csl : 1;
     const long long nblk = 8LL * r.nrb * csl * cdiv(r.P, 8);  // XCD-aware 1-D grid
@@ -1231,6 +1234,7 @@ int launch_row8(const RowArgs5 &r0, int S, hipStream_t s) {
 template <bool kIdx>
 int launch_row9(const RowArgs5 &r0, int S, hipStream_t s) {
     RowArgs5 r = r0;
+    PCR_REQUIRE(r.ich == S || r.ich == 2 * S + 1, PCR_ERR_ARG, "featnn_row9: image of %d chunks per tile", r.ich);
     r.nrb = cdiv(cdiv(r.Rmax, 32), 8 * 2);  // 8 waves x 2 row tiles per workgroup
     const long long nblk = 8LL * r.nrb * cdiv(r.P, 8);  // XCD-aware 1-D grid
     PCR_REQUIRE(nblk < (1LL << 31), PCR_ERR_ARG, "feature_corres: grid too large");

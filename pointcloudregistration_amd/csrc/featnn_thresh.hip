@@ -78,7 +78,7 @@ __device__ __forceinline__ void lds_store(unsigned addr, int v) {
 
 template <int S, bool kIdx>
 __global__ __launch_bounds__(512) void featnn_thresh9(RowArgs5 a) {
-    constexpr int NM = 2 * S + 1, NB = S, W = 8, RT = 2, G = kThreshG, GS = G / 2;
+    constexpr int NB = S, W = 8, RT = 2, G = kThreshG, GS = G / 2;
     constexpr int kT = G * NB * 64;     // f16x8 of a buffer's fragments
     constexpr int kRows = W * RT * 32;  // rows of a block round: one per thread
     static_assert(G % 2 == 0 && kRows == 512, "whole steps; the flush is one row per thread");
@@ -107,7 +107,8 @@ __global__ __launch_bounds__(512) void featnn_thresh9(RowArgs5 a) {
     const int wid = threadIdx.x >> 6, l = threadIdx.x & 63, h = l >> 5;
     const int ntl = (nr + 31) >> 5;
     const int *rl = a.rlist + (size_t)p * a.Rmax;
-    const f16x8 *bimg = a.Bp + (size_t)p * a.ntc * NM * 64 + l;
+    const int nm = a.ich;  // the image's tile stride in chunks
+    const f16x8 *bimg = a.Bp + (size_t)p * a.ntc * nm * 64 + l;
     const float *ctp = a.cct + (size_t)p * a.ntc * 32 + l;
     // group grp of the slice into buffer bufi: tiles [2 sg, 2 min(sg + GS, s1))
     // (all below 2 nst <= ntc: inside the pair's image and terms)
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(512) void featnn_thresh9(RowArgs5 a) {
             const int g = c / NB, cc = c - g * NB;
             if (sg + (g >> 1) < s1)
                 __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void *)(bimg + ((size_t)(2 * sg + g) * NM + cc) * 64),
+                    (const __attribute__((address_space(1))) void *)(bimg + ((size_t)(2 * sg + g) * nm + cc) * 64),
                     (__attribute__((address_space(3))) void *)(Bs + c * 64), 16, 0, 0);
         }
     };
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(512) void featnn_thresh9(RowArgs5 a) {
                 thr[t] = thresh_bits_up((double)__uint_as_float(B1[t]) + bnd * (1.0 + 0x1p-20));
                 live[t] = thr[t] < 0x7f800000u;
             }
-            row_operand1<S>(a, p, row, valid, h, A[t]);
+            row_operand<S, 3>(a, p, row, valid, h, A[t]);
             am[t] = 0xffffffffu;  // pass 1: the first column whose value is B1
             nh[t] = 0;            // this lane's hits in this slice
         }

@@ -53,6 +53,12 @@ namespace {
 // k = 16 chunk + 8 (l>>5) + j); padded tiles are valid encodings of +inf
 // rows, so no loop has a tail.  Grid: 1-D, XCD-aware: all row blocks of a
 // pair run on one XCD, whose L2 then holds that pair's B image (1.8 MB).
+// Compact image (round 11): featnn_row9 with the threshold route reads the hi
+// segment only, so for it the packs store S chunks per tile, [-2hi] / [hi] (the
+// same bits as the full image's first S chunks), and the tile stride is S
+// chunks.  V5Buf::ich / RowArgs5::ich carry the stored chunks per tile; every
+// reader of the lo or norm chunks (the dual screen, featnn_row8, featnn_row7)
+// requires ich = NM.
 // ---------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -225,8 +231,9 @@ struct RescanArgs5 {
 
 // the row screens' arguments (the mutual path: feature_corres_v5 in featnn.hip)
 struct RowArgs5 {
-    const f16x8 *Ap;            // row operand (register-resident): [P][ntr][NM][64]
-    const f16x8 *Bp;            // column operand (LDS-streamed): [P][ntc][NM][64]
+    const f16x8 *Ap;            // row operand (register-resident): [P][ntr][ich][64]
+    const f16x8 *Bp;            // column operand (LDS-streamed): [P][ntc][ich][64]
+    int ich;                    // stored chunks per tile of both images: NM, or S (compact: the hi segment only)
     const float *rnr;           // scaled row norms, [P][ntr * 32] by original row index
     const unsigned *cmax;       // per pair max scaled column norm (f32 bits)
     const int32_t *n_rows, *n_cols;
@@ -283,7 +290,8 @@ namespace {
 // its -2 f16(x) chunks exactly as the packs store them (row_frags) -- one
 // 128-byte line per row where the packed image spreads it over S lines: the
 // regroup gathers rows.  The sweep, the regroup and the threshold sweep all
-// build it here, so their MFMA chains agree bit for bit.  (No norm chunk:
+// take it from here or from the image (row_operand below: the same bits), so
+// their MFMA chains agree bit for bit.  (No norm chunk:
 // featnn_row9 takes the columns' |y|^2 + B as the MFMA's accumulator input and
 // leaves |x|^2 out.)
 template <int S>
@@ -320,6 +328,29 @@ __device__ __forceinline__ void row_operand1(const RowArgs5 &a, int p, int row, 
         }
 }
 
+// The same operand from the row cloud's own packed image (a.Ap: its first S
+// chunks per tile are these bits by the packs' definition, whichever layout):
+// S 16-byte fragments per lane, no conversion.  PCR_ROW_IMG selects it per
+// kernel at compile time -- bit 0 featnn_row9 pass 1, bit 1 featnn_row9 pass 2,
+// bit 2 featnn_regroup9, bit 3 featnn_thresh9.  Measured per slot (DESIGN.md
+// Round 11): pass 1's sweep gains 0.02 ms per 256-pair step and keeps it; pass
+// 2's gain is inside three run-to-run ranges at 256 pairs; the regroups and the
+// threshold sweeps, which gather their rows, lose at 256 pairs.
+#ifndef PCR_ROW_IMG
+#define PCR_ROW_IMG 1
+#endif
+template <int S>
+__device__ __forceinline__ void row_operand_img(const RowArgs5 &a, int p, int row, int h, f16x8 (&A)[S]) {
+    const f16x8 *q = a.Ap + ((size_t)p * a.ntr + (row >> 5)) * a.ich * 64 + (row & 31) + 32 * h;  // row < 32 ntr
+#pragma unroll
+    for (int c = 0; c < S; ++c) A[c] = q[(size_t)c * 64];
+}
+template <int S, int kBit>
+__device__ __forceinline__ void row_operand(const RowArgs5 &a, int p, int row, bool valid, int h, f16x8 (&A)[S]) {
+    if constexpr ((PCR_ROW_IMG >> kBit) & 1) row_operand_img<S>(a, p, row, h, A);
+    else row_operand1<S>(a, p, row, valid, h, A);
+}
+
 // the row's certificate bound (bound_ct) from a screen's arguments
 __device__ __forceinline__ double row_bound_ct(const RowArgs5 &a, int p, int row, float rexv, int Kt) {
     const double sub = sub_term(a.D);
@@ -334,6 +365,7 @@ __device__ __forceinline__ double row_bound_ct(const RowArgs5 &a, int p, int row
 // dual screen and the mutual path)
 struct V5Buf {
     int S, NM, NX, W, nrb, ntn, ntm, ctbits;  // S chunks per D-segment, NM stored, NX executed
+    int ich;  // chunks per tile the images hold: NM, or S when compact (v5_prepare)
     Split5 sp;
     f16x8 *Ap, *Bp;
     float *fnr, *gnr;
@@ -346,9 +378,10 @@ struct V5Buf {
     float *cbias;                        // [P] their B (feat_colterms)
 };
 
-// featnn_pack.hip
+// featnn_pack.hip; compact: the images hold the hi segment only (S chunks per
+// tile) -- for featnn_row9 with the threshold route, which reads nothing else
 int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D, const int32_t *n_src,
-               const int32_t *n_tgt, hipStream_t s, V5Buf &v);
+               const int32_t *n_tgt, hipStream_t s, V5Buf &v, bool compact = false);
 // featnn_dual.hip
 int feature_match_v5(const float *F, const float *G, int P, int Nmax, int Mmax, int D, const int32_t *n_src,
                      const int32_t *n_tgt, int32_t *nn12, int32_t *nn21, hipStream_t s);

@@ -1,0 +1,242 @@
+"""The compact f16 operand image of the 1-term feature screens
+(csrc/featnn_pack.hip): on the default route of
+pcr_feature_correspondences (featnn_row9 + the threshold route, D <= 32) the
+packs store only the hi segment, S = ceil(D / 16) chunks per 32-row tile, and
+featnn_row9, featnn_regroup9 and featnn_thresh9 walk the images with that tile
+stride.  Every other route keeps the full image of 2 S + 1 chunks;
+PCR_FEAT_IMAGE=full keeps it on the default route too.
+
+Bar: the stored hi bits are the full image's, so every screened value is too --
+the default route and PCR_FEAT_IMAGE=full agree byte for byte in nn12, the
+correspondences and the mutual stage's scratch (v12, e12, wq of the screened
+columns, the column and row flags, pcr_featmut_debug_copy), and both equal the
+oracle (`_check` of test_featthresh_gpu.py: the default and the 3-term route).
+pcr_featnn_image_chunks() tells which layout a call packed.
+
+Shapes: the smallest at which a tile stride can go wrong -- more than one
+16-tile LDS group in both passes with a short last group (530 x 552), 1 and 9
+pairs (9: the p >= P exits of the 8 XCD slots), every descriptor width with a
+path of its own (32: the register pack; 20: the generic pack with a zero tail;
+16 and 8: S = 1; 48: S = 3, featnn_row7, full image), ragged counts with 0, 1
+and 33, the repair launch, non-finite rows, the workspace re-laid-out between
+routes, and the near twins that give the threshold kernels work."""
+import numpy as np
+import pytest
+
+from pointcloudregistration_amd import _lib
+from pointcloudregistration_amd import registration as reg
+from test_featthresh_gpu import _MEMO, _check, _np, _run, _twin_batch
+
+
+def _chunks(D, compact):
+    S = (D + 15) // 16
+    return S if compact and S <= 2 else 2 * S + 1
+
+
+def _scratch(P, Nmax, Mmax):
+    """feature_corres_v5's scratch of the last call: v12 [P][Nmax] f64 | e12
+    [P][Nmax] f32 | wq [P][Mmax] float4 (16-byte aligned) | used, pos [P][Mmax +
+    1] | jlist, nn21x [P][Mmax] | flag [P][Nmax + 1] (as raw bytes / ints)."""
+    import torch
+    pn, pm = P * Nmax, P * Mmax
+    o_wq = ((12 * pn + 15) // 16) * 16
+    o_used = o_wq + 16 * pm
+    o_flag = o_used + 4 * (2 * (pm + P) + 2 * pm)
+    total = o_flag + 4 * (pn + P)
+    buf = torch.empty(total, dtype=torch.uint8, device="cuda")
+    _lib.call("pcr_featmut_debug_copy", buf.data_ptr(), buf.numel(), _lib.stream_handle())
+    torch.cuda.synchronize()
+    raw = _np(buf)
+    return {"v12": raw[:8 * pn].view(np.uint64).reshape(P, Nmax),
+            "e12": raw[8 * pn:12 * pn].view(np.uint32).reshape(P, Nmax),
+            "wq": raw[o_wq:o_used].view(np.uint32).reshape(P, Mmax, 4),
+            "used": raw[o_used:o_used + 4 * (pm + P)].view(np.int32).reshape(P, Mmax + 1).copy(),
+            "flag": raw[o_flag:total].view(np.int32).reshape(P, Nmax + 1).copy()}
+
+
+def _call(F, G, ns, nt):
+    """One pcr_feature_correspondences call: its outputs, scratch and layout."""
+    nn, nc, co = _run(F, G, ns, nt)
+    return {"nn": nn, "nc": nc, "co": co, "sc": _scratch(F.shape[0], F.shape[1], G.shape[1]),
+            "chunks": _lib.featnn_image_chunks()}
+
+
+def _same(a, b, cs, ct):
+    """Two calls agree byte for byte in everything the call defines: rows below
+    a pair's counts, correspondences below n_corres, wq where pass 2 screened
+    the column (used 1 / 2).  A pair without sources or targets has no screen."""
+    assert np.array_equal(a["nc"], b["nc"])
+    for p in range(len(cs)):
+        n, m = int(cs[p]), int(ct[p])
+        assert np.array_equal(a["nn"][p, :n], b["nn"][p, :n]), p
+        k = int(a["nc"][p])
+        assert np.array_equal(a["co"][p, :k], b["co"][p, :k]), p
+        if n == 0 or m == 0:
+            continue
+        sa, sb = a["sc"], b["sc"]
+        assert np.array_equal(sa["v12"][p, :n], sb["v12"][p, :n]), p
+        assert np.array_equal(sa["e12"][p, :n], sb["e12"][p, :n]), p
+        assert np.array_equal(sa["used"][p, :m], sb["used"][p, :m]), p
+        assert np.array_equal(sa["flag"][p, :n + 1], sb["flag"][p, :n + 1]), p
+        scr = (sa["used"][p, :m] == 1) | (sa["used"][p, :m] == 2)
+        assert np.array_equal(sa["wq"][p, :m][scr], sb["wq"][p, :m][scr]), p
+
+
+def _compact_vs_full(oracle, monkeypatch, key, F, G, ns=None, nt=None, oracle_pairs=None):
+    """The default route (compact image at S <= 2) against PCR_FEAT_IMAGE=full,
+    byte for byte, and both -- with the 3-term route -- against the oracle.
+    oracle_pairs: the leading pairs the oracle takes (none of them empty)."""
+    P, D = F.shape[0], F.shape[2]
+    cs = np.full(P, F.shape[1], np.int32) if ns is None else ns
+    ct = np.full(P, G.shape[1], np.int32) if nt is None else nt
+    a = _call(F, G, ns, nt)
+    assert a["chunks"] == _chunks(D, True), a["chunks"]
+    monkeypatch.setenv("PCR_FEAT_IMAGE", "full")
+    b = _call(F, G, ns, nt)
+    monkeypatch.delenv("PCR_FEAT_IMAGE")
+    assert b["chunks"] == _chunks(D, False), b["chunks"]
+    _same(a, b, cs, ct)
+    e = P if oracle_pairs is None else oracle_pairs
+    sub = (F[:e], G[:e], None if ns is None else ns[:e], None if nt is None else nt[:e])
+    fb, rs = _check(oracle, monkeypatch, key, *sub)  # default, then PCR_FEAT_THRESH=0: the full image
+    assert _lib.featnn_image_chunks() == _chunks(D, False)
+    exp = _MEMO[key]
+    for p in range(e):
+        e12, ec = exp[p]
+        assert np.array_equal(a["nn"][p, :cs[p]], e12), p
+        assert int(a["nc"][p]) == len(ec) and np.array_equal(a["co"][p, :len(ec)], ec), p
+    return a, fb, rs
+
+
+def _codebook(rng, P, n, m, D, noise=0.6):
+    """Noisy copies of a shared code book (as test_random_descriptors_ragged),
+    and in each cloud a quarter of the rows are twins 1e-2 away from another
+    row of that cloud: rows (target twins) and J columns (source twins) the
+    1-term certificate fails, with two or three candidates each."""
+    code = rng.standard_normal((P, max(n, m) + 40, D)).astype(np.float32)
+    F = (np.stack([code[p, rng.permutation(code.shape[1])[:n]] for p in range(P)]) +
+         rng.normal(0, noise, (P, n, D))).astype(np.float32)
+    G = (np.stack([code[p, rng.permutation(code.shape[1])[:m]] for p in range(P)]) +
+         rng.normal(0, noise, (P, m, D))).astype(np.float32)
+    for X in (F, G):
+        k = X.shape[1] // 4
+        for p in range(P):
+            idx = rng.permutation(X.shape[1])[:2 * k]
+            X[p, idx[k:]] = X[p, idx[:k]] + (1e-2 * rng.standard_normal((k, D))).astype(np.float32)
+    return F, G
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", [1, 9])
+def test_lds_groups(oracle, monkeypatch, P):
+    """530 x 552, D = 32: 17 / 18 column tiles are two 16-tile LDS groups in
+    both passes, the last one short; neither count is a multiple of 32."""
+    rng = np.random.default_rng(1100 + P)
+    F, G = _codebook(rng, P, 530, 552, 32)
+    _, fb, _ = _compact_vs_full(oracle, monkeypatch, ("compact_groups", P), F, G)
+    assert fb[0] > 0 and fb[1] > 0, fb  # the regroup's leftovers reached featnn_thresh9 in both passes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [32, 20, 16, 8, 48])
+def test_descriptor_widths(oracle, monkeypatch, D):
+    """Each width with a path of its own, three pairs of 257 x 290 (nine row
+    tiles, ten column tiles).  D = 48 (S = 3) runs featnn_row7 on the full
+    image with or without the hook."""
+    rng = np.random.default_rng(1200 + D)
+    F, G = _codebook(rng, 3, 257, 290, D, noise=0.6 if D >= 16 else 0.2)
+    a, _, _ = _compact_vs_full(oracle, monkeypatch, ("compact_width", D), F, G)
+    assert a["chunks"] == {32: 2, 20: 2, 16: 1, 8: 1, 48: 7}[D]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [32, 20, 16])
+def test_ragged_counts(oracle, monkeypatch, D):
+    """Counts with 0, 1 and 33 in both clouds.  Past a pair's count each cloud
+    holds exact copies of rows of the other (distance 0: as an argmin they
+    would win).  The pairs with an empty cloud come last: no oracle call on
+    them, the two layouts still agree and a pair without targets gives index 0."""
+    rng = np.random.default_rng(1300 + D)
+    n, m = 97, 203
+    ca = np.array([97, 1, 33, 64, 33, 0, 50], np.int32)
+    cb = np.array([150, 203, 1, 33, 65, 77, 0], np.int32)
+    P = len(ca)
+    F, G = _codebook(rng, P, n, m, D)
+    for p in range(P):
+        if ca[p] and cb[p] < m:
+            G[p, cb[p]:] = F[p, rng.integers(0, ca[p], m - cb[p])]
+        if cb[p] and ca[p] < n:
+            F[p, ca[p]:] = G[p, rng.integers(0, cb[p], n - ca[p])]
+    a, _, _ = _compact_vs_full(oracle, monkeypatch, ("compact_ragged", D), F, G, ca, cb, oracle_pairs=5)
+    assert not a["nn"][6, :ca[6]].any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [32, 20, 16])
+def test_repair_pass_restores_the_compact_image(oracle, monkeypatch, D):
+    """Pair 1 has an element 64 x its sample's maximum (the first 64 rows of
+    both clouds) in row 100: the first pack flags the pair and the repair
+    launch packs it again at the scale of its full maximum -- in the layout of
+    the first launch -- beside two ordinary pairs."""
+    rng = np.random.default_rng(1400 + D)
+    F, G = _codebook(rng, 3, 200, 257, D)
+    big = 64.0 * max(np.abs(F[1, :64]).max(), np.abs(G[1, :64]).max())
+    F[1, 100, D // 2] = big
+    G[1, 130, 1] = -big
+    _compact_vs_full(oracle, monkeypatch, ("compact_repair", D), F, G)
+
+
+@pytest.mark.gpu
+def test_nonfinite_pairs_beside_finite_ones(oracle, monkeypatch):
+    """A NaN row in pair 0's sources, an inf element in pair 2's targets, pairs
+    1 and 3 finite."""
+    rng = np.random.default_rng(1500)
+    F, G = _codebook(rng, 4, 200, 257, 32)
+    F[0, 70] = np.nan
+    G[2, 140, 31] = np.inf
+    _compact_vs_full(oracle, monkeypatch, ("compact_nonfinite",), F, G)
+
+
+@pytest.mark.gpu
+def test_workspace_relayout_between_routes(oracle, monkeypatch):
+    """One process, the same shapes: the default route, PCR_FEAT_THRESH=0,
+    pcr_feature_match, the default route again.  Each call lays the pack's
+    workspace slot out anew (compact, full, full, compact); every result equals
+    the first of its kind."""
+    rng = np.random.default_rng(1600)
+    F, G = _codebook(rng, 3, 290, 257, 32)
+    cs = ct = None
+    a = _call(F, G, cs, ct)
+    assert a["chunks"] == 2
+    monkeypatch.setenv("PCR_FEAT_THRESH", "0")
+    b = _call(F, G, cs, ct)
+    monkeypatch.delenv("PCR_FEAT_THRESH")
+    assert b["chunks"] == 5
+    nn12, nn21 = (_np(t) for t in reg.feature_match(F, G))
+    assert _lib.featnn_image_chunks() == 5
+    c = _call(F, G, cs, ct)
+    assert c["chunks"] == 2
+    full = np.full(3, 290, np.int32), np.full(3, 257, np.int32)
+    _same(a, c, *full)
+    assert np.array_equal(a["nn"], b["nn"]) and np.array_equal(a["nn"], nn12)
+    assert np.array_equal(a["nc"], b["nc"])
+    for p in range(3):
+        e12, e21 = oracle.featnn(F[p], G[p]), oracle.featnn(G[p], F[p])
+        ec = oracle.corres(e12, e21, True, 3)
+        assert np.array_equal(nn12[p], e12) and np.array_equal(nn21[p], e21), p
+        for r in (a, b, c):
+            assert int(r["nc"][p]) == len(ec) and np.array_equal(r["co"][p, :len(ec)], ec), p
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", [1, 9])
+@pytest.mark.parametrize("sep,twin_src", [(1e-2, False), (1e-6, True)])
+def test_thresholds_on_near_twins(oracle, monkeypatch, sep, twin_src, P):
+    """The near twins of test_featthresh_gpu: most rows fail the 1-term
+    certificate, so featnn_thresh9 and featnn_exact_cand settle them from the
+    compact image; no row of pass 1 reaches the exact rescan."""
+    F, G = _twin_batch(9, sep, twin_src)
+    F, G = F[:P], G[:P]
+    _, (r12, _), (x12, _) = _compact_vs_full(oracle, monkeypatch, ("twins", sep, twin_src, P), F, G)
+    assert r12 > P * F.shape[1] // 2, r12
+    assert x12 == 0, x12
