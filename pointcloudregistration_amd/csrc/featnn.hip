@@ -13,7 +13,9 @@
 // error, and recompute every uncertified row / column exactly in f64.
 //
 // Units (D <= 64: the f16 x3 split screen on v_mfma_f32_32x32x16_f16):
-//   featnn_v5.h        operand layout, bounds, argument structs, cross-unit entry points
+//   featnn_v5.h        operand layout, bounds, argument structs, the per-cloud sides (V5Buf),
+//                      cross-unit entry points
+//   featnn_route.h     host only: the route's constants, the tile padding, the PCR_FEAT_* hooks (feat_route)
 //   featnn_pack.hip    scale, packed operands, norms, column terms   (v5_prepare)
 //   featnn_dual.hip    both directions in one screen                 (feature_match_v5)
 //   featnn_row.hip     one direction's rows: featnn_row7 / row8 / row9 (launch_row*)
@@ -23,13 +25,12 @@
 //   featnn_f32.hip     64 < D <= 128: augmented f32 operands on v_mfma_f32_32x32x2_f32
 // Call paths:
 //   pcr_feature_match            v5_prepare -> feature_match_v5's dual screen -> run_rescan
-//   pcr_feature_correspondences  v5_prepare -> row screen pass 1 -> run_rescan (rows) -> featmut_jbuild
-//                                -> row screen pass 2 -> featmut_resolve -> run_rescan (columns)
-//                                -> featmut_corres        (feature_corres_v5 below)
+//   pcr_feature_correspondences  feat_route -> v5_prepare -> row screen pass 1 (screen_args, run_pass)
+//                                -> run_rescan (rows) -> featmut_jbuild -> row screen pass 2 (the sides
+//                                exchanged) -> featmut_resolve -> run_rescan (columns) -> featmut_corres
+//                                (feature_corres_v5 below)
 #include "featnn_v5.h"
 #include "scan.h"
-#include <stdlib.h>
-#include <string.h>
 #include <algorithm>
 
 namespace pcr {
@@ -201,77 +202,6 @@ __global__ __launch_bounds__(1024) void featmut_corres(MutArgs a) {
 
 }  // namespace
 
-// column slices of the 3-term screens' list mode: a pair's short list is
-// one workgroup per slice -- at 256 pairs one slice (the chip is full), at
-// 32 pairs 8 (one block per pair left 224 CUs idle: ~0.2 ms per launch)
-static int list_slices(int P) { return std::max(1, std::min(8, 256 / std::max(P, 1))); }
-
-// PCR_FEAT_ROW9=0: the round-6 featnn_row8 1-term passes (A/B; read per call)
-static bool feat_row9() {
-    const char *e = getenv("PCR_FEAT_ROW9");
-    return !(e && e[0] == '0');
-}
-
-// a 3-term fallback screen (list mode), in its profile slot
-template <bool kIdx>
-static int launch_fallback(const RowArgs5 &r, int S, hipStream_t q, int slot) {
-    prof_begin(q, slot);
-    const int rc = launch_row8<kIdx, false>(r, S, q);
-    prof_end(q, slot);
-    return rc;
-}
-
-// side(q) then main() on s; with PCR_FEAT_BESIDE=1, side(q) on the second
-// side stream beside main() on s, joined back into s.  Measured (featnn_bench,
-// mutual): 256 pairs 3.42 ms either way, 32 pairs 0.778 beside vs 0.755 ms in
-// order -- the 3-term screen and the regroup compete for the same CUs, so the
-// default is in order
-template <class Side, class Main>
-static int beside(hipStream_t s, Side side, Main main) {
-    static const bool off = [] {
-        const char *e = getenv("PCR_FEAT_BESIDE");
-        return !(e && e[0] == '1');
-    }();
-    hipStream_t q = s;
-    hipEvent_t ef = nullptr, ej = nullptr;
-    int rc = off ? PCR_OK : side_stream(&q, &ef, &ej, 2);
-    if (rc != PCR_OK) return rc;
-    if (q != s) {
-        PCR_HIP_CHECK(hipEventRecord(ef, s));
-        PCR_HIP_CHECK(hipStreamWaitEvent(q, ef, 0));
-    }
-    if ((rc = side(q)) != PCR_OK) return rc;
-    if (q != s) PCR_HIP_CHECK(hipEventRecord(ej, q));
-    prof_begin(s, kProfFeatRegroup);
-    rc = main();
-    prof_end(s, kProfFeatRegroup);
-    if (rc != PCR_OK) return rc;
-    if (q != s) PCR_HIP_CHECK(hipStreamWaitEvent(s, ej, 0));
-    return PCR_OK;
-}
-
-// the threshold route behind featnn_row9 (featnn_thresh.hip): on by default,
-// PCR_FEAT_THRESH=0 for the 3-term screens of its leftover rows (A/B, parity;
-// read per call)
-static bool feat_thresh() {
-    const char *e = getenv("PCR_FEAT_THRESH");
-    return !(e && e[0] == '0');
-}
-
-// PCR_FEAT_IMAGE=full: the full 2S + 1 chunk image on the default route too
-// (A/B, the parity tests; read per call)
-static bool feat_image_full() {
-    const char *e = getenv("PCR_FEAT_IMAGE");
-    return e && strcmp(e, "full") == 0;
-}
-
-// the 1-term screens in front of the 3-term ones (S <= 2): on by default,
-// PCR_FEAT_ONE=0 for the round-5 path (A/B, the parity tests; read per call)
-static bool feat_one_term() {
-    const char *e = getenv("PCR_FEAT_ONE");
-    return !(e && e[0] == '0');
-}
-
 // ---------------------------------------------------------------------------
 // Mutual correspondences without the column screen (feature_corres_v5).
 //
@@ -291,51 +221,54 @@ static bool feat_one_term() {
 //   A column that cannot be decided is rescanned exactly (featnn_rescan3,
 //   direction 1) and its candidates compared with that argmin.
 // The result is the same set corres_build forms from the exact nn12 / nn21.
+//
+// The driver: feat_route (featnn_route.h) decides the route, v5_prepare packs
+// both clouds into V5Buf::side[2], and a pass in direction dir is the rows of
+// side[dir] against the columns of side[1 - dir] (screen_args) with that pass's
+// outputs -- pass 2 is pass 1 with the sides exchanged.
 // ---------------------------------------------------------------------------
 
-// One pass of the row screens on s (kIdx: pass 1), timed in `slot`:
-//   use9    featnn_row9's sweep, then the 3-term screen of the rows it listed
-//           (in `slot_fb`) beside the regroup and finish, whose failing rows go
-//           to llist / lcount;
-//   one     featnn_row8's 1-term pass, then the 3-term screen of the rows it listed;
-//   S <= 2  the 3-term featnn_row8 alone;  S > 2  featnn_row7.
-// r: the pass's screen; fb: its 3-term fallback over the list r fills.
-// th (use9 only, null with PCR_FEAT_THRESH=0): the threshold route instead of
-// the 3-term screen -- the finish appends its failing rows to the sweep's own
-// list, then featnn_thresh9 + featnn_exact_cand settle that list (in `slot_fb`),
-// all in order on s; th->llist / lcount take the rows they leave (pass 1).
-template <bool kIdx>
-static int run_pass(const RowArgs5 &r, const RowArgs5 &fb, int S, bool one, bool use9, int slot, int slot_fb,
-                    int *llist, int *lcount, hipStream_t s, const RowArgs5 *th = nullptr) {
-    int rc;
-    prof_begin(s, slot);
-    if (use9) {
-        PCR_HIP_CHECK(hipMemsetAsync(r.bcnt, 0, sizeof(int) * (size_t)r.P * (r.ntc / 2), s));  // a count per step
-        if ((rc = launch_row9<kIdx>(r, S, s)) != PCR_OK) return rc;
-        prof_end(s, slot);
-        if (th) {
-            RowArgs5 rg = r;
-            rg.llist = r.list; rg.lcount = r.count; rg.thresh = 1;
-            prof_begin(s, kProfFeatRegroup);
-            rc = launch_regroup9<kIdx>(rg, S, s);
-            prof_end(s, kProfFeatRegroup);
-            if (rc != PCR_OK) return rc;
-            prof_begin(s, slot_fb);
-            rc = launch_thresh9<kIdx>(*th, S, s);
-            prof_end(s, slot_fb);
-            return rc;
-        }
-        RowArgs5 rg = r;
-        rg.llist = llist; rg.lcount = lcount;
-        return beside(s, [&](hipStream_t q) { return launch_fallback<kIdx>(fb, S, q, slot_fb); },
-                      [&] { return launch_regroup9<kIdx>(rg, S, s); });
-    }
-    if (one) rc = launch_row8<kIdx, true>(r, S, s);
-    else if (S <= 2) rc = launch_row8<kIdx, false>(r, S, s);
-    else rc = launch_row7<kIdx>(r, S, s);
-    if (rc != PCR_OK) return rc;
-    prof_end(s, slot);
-    return one ? launch_fallback<kIdx>(fb, S, s, slot_fb) : PCR_OK;
+// what a pass writes, and the scratch both passes share
+struct PassIO {
+    int32_t *nn = nullptr, *nns = nullptr;  // pass 1: the screened argmin and its copy for featmut_jbuild,
+    double *v = nullptr;                    // its value and error bound
+    float *e = nullptr;
+    float4 *wq = nullptr;                           // pass 2: top-2 values of its rows,
+    const int *rlist = nullptr, *rcount = nullptr;  // the list J
+    int *bcnt = nullptr;                    // featnn_row9's bucket counts and entries,
+    uint4 *blist = nullptr, *rec = nullptr, *part = nullptr;  // the regroup's records, the slices' partials
+    int *cand = nullptr;                    // featnn_thresh9's candidate slots
+};
+
+// featnn_row9's buckets (a pass's rows by winning step): 4x a bucket's mean
+// row count, at least 64 rows; a fuller bucket sends rows to the 3-term screen
+static int bucket_cap(const V5Side &row, const V5Side &col) { return std::max(64, 4 * cdiv(row.Nmax, col.nt / 2)); }
+
+// The screen of one pass: the rows of side[dir] (register operand, role dir)
+// against every column of side[1 - dir].  The only place RowArgs5 is filled
+// field by field; what is not set keeps its default (nrb: each launcher sets
+// its own).
+static RowArgs5 screen_args(const V5Buf &v, int dir, const FeatRoute &rt, const PassIO &o) {
+    const V5Side &row = v.side[dir], &col = v.side[1 - dir];
+    RowArgs5 r;
+    r.Ap = row.Xp; r.Bp = col.Xp; r.ich = v.ich;
+    r.rnr = row.nr; r.cmax = col.nmax; r.cemax = col.emax;
+    r.n_rows = row.n; r.n_cols = col.n;
+    r.P = v.P; r.Rmax = row.Nmax; r.Cmax = col.Nmax; r.ntr = row.nt; r.ntc = col.nt; r.D = v.D;
+    // the column-tile code in pass 1's values (G's tiles); pass 2 keeps values only and carries the same width
+    r.ctbits = 1;
+    while ((1 << r.ctbits) < v.side[1].nt) ++r.ctbits;
+    r.Xr = row.X; r.Xc = col.X; r.sc = v.mx; r.role = dir; r.cs = v.sp.cs;  // featnn_row8 builds its rows from the cloud
+    r.rre = row.re; r.rct = row.ct; r.cct = col.ct; r.cbias = v.cbias;
+    r.rlist = o.rlist; r.rcount = o.rcount;
+    r.nn = o.nn; r.nns = o.nns; r.v = o.v; r.e = o.e; r.wq = o.wq;
+    // a 1-term screen lists the rows it leaves to the 3-term one; the 3-term screen alone lists pass 1's
+    // rows for the exact rescan and nothing in pass 2 (values only: the resolve decides)
+    r.list = rt.one ? (dir ? v.fbl21 : v.fbl12) : (dir ? nullptr : v.list12);
+    r.count = rt.one ? (dir ? v.fbc21 : v.fbc12) : (dir ? nullptr : v.cnt12);
+    r.bcnt = o.bcnt; r.bcap = bucket_cap(row, col); r.blist = o.blist; r.rec = o.rec;
+    r.csl = 1; r.part = o.part; r.cand = o.cand;
+    return r;
 }
 
 // the 3-term screen (featnn_row8 list mode, row-block-major, fsl column
@@ -348,62 +281,119 @@ static RowArgs5 fallback_args(RowArgs5 r, int *list, int *count, int fbdiag, int
     return r;
 }
 
+// the threshold route's view of a pass: the rows r lists; what it leaves goes to list / count
+static RowArgs5 thresh_args(RowArgs5 t, int *list, int *count) {
+    t.rlist = t.list; t.rcount = t.count;
+    t.llist = list; t.lcount = count;
+    return t;
+}
+
+// One pass as run_pass takes it: the screen r, its 3-term fallback view fb and
+// its threshold view th (the table at RowArgs5), the profile slots of the screen
+// and of whichever settles its list, and where the rows go that no screen
+// settles -- pass 1: the exact rescan's list; pass 2: nowhere, the resolve sends
+// an undecided column to the exact column rescan
+struct Pass {
+    RowArgs5 r, fb, th;
+    int slot, slot_fb;
+    int *list, *count;
+};
+static Pass make_pass(const RowArgs5 &r, int dir, const FeatRoute &rt, int *list, int *count) {
+    return {r, fallback_args(r, list, count, dir + 1, rt.fsl), thresh_args(r, list, count),
+            dir ? kProfFeatScreen2 : kProfFeatScreen, dir ? kProfFeatScreen2b : kProfFeatScreen1b, list, count};
+}
+
+// a 3-term fallback screen (list mode), in its profile slot
+template <bool kIdx>
+static int launch_fallback(const RowArgs5 &r, int S, hipStream_t q, int slot) {
+    prof_begin(q, slot);
+    const int rc = launch_row8<kIdx, false>(r, S, q);
+    prof_end(q, slot);
+    return rc;
+}
+
+// One pass of the row screens, in order on s (kIdx: pass 1), timed in p.slot:
+//   use9, thresh   featnn_row9's sweep; the regroup and finish, which appends its
+//                  failing rows to the sweep's own list; featnn_thresh9 +
+//                  featnn_exact_cand settle that list (in p.slot_fb)
+//   use9           the sweep; the 3-term screen of the rows it listed (p.slot_fb);
+//                  the regroup and finish, whose failing rows go to p.list
+//   one            featnn_row8's 1-term pass, then the 3-term screen of the rows it listed
+//   S <= 2         the 3-term featnn_row8 alone;  S > 2  featnn_row7
+template <bool kIdx>
+static int run_pass(const FeatRoute &rt, const Pass &p, hipStream_t s) {
+    const int S = rt.S;
+    int rc;
+    prof_begin(s, p.slot);
+    if (rt.use9) {
+        PCR_HIP_CHECK(hipMemsetAsync(p.r.bcnt, 0, sizeof(int) * (size_t)p.r.P * (p.r.ntc / 2), s));  // a count per step
+        if ((rc = launch_row9<kIdx>(p.r, S, s)) != PCR_OK) return rc;
+        prof_end(s, p.slot);
+        RowArgs5 rg = p.r;
+        if (rt.thresh) {
+            rg.llist = p.r.list; rg.lcount = p.r.count; rg.thresh = 1;
+        } else {
+            rg.llist = p.list; rg.lcount = p.count;
+            if ((rc = launch_fallback<kIdx>(p.fb, S, s, p.slot_fb)) != PCR_OK) return rc;
+        }
+        prof_begin(s, kProfFeatRegroup);
+        rc = launch_regroup9<kIdx>(rg, S, s);
+        prof_end(s, kProfFeatRegroup);
+        if (rc != PCR_OK || !rt.thresh) return rc;
+        prof_begin(s, p.slot_fb);
+        rc = launch_thresh9<kIdx>(p.th, S, s);
+        prof_end(s, p.slot_fb);
+        return rc;
+    }
+    if (rt.one) rc = launch_row8<kIdx, true>(p.r, S, s);
+    else if (S <= 2) rc = launch_row8<kIdx, false>(p.r, S, s);
+    else rc = launch_row7<kIdx>(p.r, S, s);
+    if (rc != PCR_OK) return rc;
+    prof_end(s, p.slot);
+    return rt.one ? launch_fallback<kIdx>(p.fb, S, s, p.slot_fb) : PCR_OK;
+}
+
 // the mutual path (see above): nn12 and the correspondences without the
 // column screen of every target
 static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
                              const int32_t *n_src, const int32_t *n_tgt, int mutual, int ransac_n,
                              int32_t *nn12, int32_t *corres, int32_t *n_corres, hipStream_t s) {
-    // The route, ahead of the prepare (it decides the images' layout): from S,
-    // the tile counts as v5_prepare pads them, and the hooks.
-    const int S0 = cdiv(D, 16), rg = std::max(kRow8G, kRow9G);
-    const int ntn0 = cdiv(cdiv(Nmax, 32), 16) * 16, ntm0 = cdiv(cdiv(Mmax, 32), rg) * rg;
-    const bool one = S0 <= 2 && feat_one_term();
-    // (the regroup keeps a pair's per-step prefix in LDS)
-    const bool use9 = one && feat_row9() && std::max(ntm0, ntn0) / 2 <= kRegroupMaxSteps;
-    const bool thresh = use9 && feat_thresh();
-    // featnn_row9 with the threshold route reads the images' hi segment only:
-    // the compact image (S chunks per tile); every other route reads lo / norms
-    const bool compact = thresh && !feat_image_full();
+    const FeatRoute rt = feat_route(P, Nmax, Mmax, D);  // ahead of the prepare: it decides the images' layout
     V5Buf v;
-    int rc = v5_prepare(F, G, P, Nmax, Mmax, D, n_src, n_tgt, s, v, compact);
+    int rc = v5_prepare(F, G, P, Nmax, Mmax, D, n_src, n_tgt, s, v, rt.compact);
     if (rc != PCR_OK) return rc;
-    const int ntn = v.ntn, ntm = v.ntm;
-    PCR_REQUIRE(v.S == S0 && ntn == ntn0 && ntm == ntm0, PCR_ERR_ARG, "feature_corres: tile counts");
+    const V5Side &f = v.side[0], &g = v.side[1];
     // scratch: v12 [P][Nmax] f64 | e12 [P][Nmax] f32 | wq [P][Mmax] float4 | used, pos
     // [P][Mmax+1] | jlist, nn21x [P][Mmax] | flag [P][Nmax+1] | nj, zero [P] | nns [P][Nmax]
+    // | featnn_row9's buckets | records | slice partials | bucket counts | candidates
     const size_t pn = (size_t)P * Nmax, pm = (size_t)P * Mmax;
-    // featnn_row9's buckets (a pass's rows by winning step): 4x a bucket's mean
-    // row count, at least 64 rows; a fuller bucket sends rows to the 3-term screen
-    const int nst1 = ntm / 2, nst2 = ntn / 2;
-    const int cap1 = std::max(64, 4 * cdiv(Nmax, nst1)), cap2 = std::max(64, 4 * cdiv(Mmax, nst2));
+    const int nst1 = g.nt / 2, nst2 = f.nt / 2;  // column steps of pass 1 / pass 2
     const size_t pb = (size_t)P * std::max(nst1, nst2);
-    const size_t pl = (size_t)P * std::max((size_t)nst1 * cap1, (size_t)nst2 * cap2);
+    const size_t pl = (size_t)P * std::max((size_t)nst1 * bucket_cap(f, g), (size_t)nst2 * bucket_cap(g, f));
     const size_t pr = (size_t)P * std::max(Nmax, Mmax);
-    const int fsl = list_slices(P);
-    const size_t pt = fsl > 1 ? (size_t)fsl * pr : 0;  // the sliced 3-term screens' partials
+    const size_t pt = rt.fsl > 1 ? (size_t)rt.fsl * pr : 0;  // the sliced 3-term screens' partials
     MutArgs ma;
-    double *v12;
-    float *e12;
-    float4 *wq;
-    int *nn21x, *zero, *bcnt, *cand;
-    int32_t *nns;
-    uint4 *blist, *rec, *part;
-    WsLayout l;  // pcr_featmut_debug_copy's readers go by these offsets
-    l.take(v12, pn); l.take(e12, pn);
-    l.take(wq, pm);  // 16-byte aligned
+    PassIO o1, o2;
+    int *nn21x, *zero;
+    WsLayout l;  // tests/featscreen_cases.py mut_scratch reads by these offsets (pcr_featmut_debug_copy)
+    l.take(o1.v, pn); l.take(o1.e, pn);
+    l.take(o2.wq, pm);  // 16-byte aligned
     l.take(ma.used, pm + P); l.take(ma.pos, pm + P);
     l.take(ma.jlist, pm); l.take(nn21x, pm);
     l.take(ma.flag, pn + P);
     l.take(ma.nj, P); l.take(zero, P);
-    l.take(nns, pn);
-    l.take(blist, pl);  // 16-byte aligned
-    l.take(rec, pr); l.take(part, pt);
-    l.take(bcnt, pb);
-    l.take(cand, thresh ? pr * kThreshK : 0);  // featnn_thresh9's candidate slots
+    l.take(o1.nns, pn);
+    l.take(o1.blist, pl);  // 16-byte aligned
+    l.take(o1.rec, pr); l.take(o1.part, pt);
+    l.take(o1.bcnt, pb);
+    l.take(o1.cand, rt.thresh ? pr * kThreshK : 0);  // featnn_thresh9's candidate slots
     bool fresh = false;
     // + 32: the tail also keeps 16 bytes per round-up (wq, blist) beyond the layout's own padding
     PCR_REQUIRE(workspace_bind(kWsFeatMutual, l, kWsSlack + 32, &fresh), PCR_ERR_NOMEM, "feature_corres: %s",
                 pcr_last_error());
+    o1.nn = nn12;
+    o2.rlist = ma.jlist; o2.rcount = ma.nj;
+    o2.blist = o1.blist; o2.rec = o1.rec; o2.part = o1.part; o2.bcnt = o1.bcnt; o2.cand = o1.cand;
     // a constant zero count per pair (read only): cleared when the slot is new
     // or was last used for fewer pairs
     static thread_local const void *z_ptr = nullptr;
@@ -414,28 +404,12 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
         z_cnt = P;
     }
     ma.nn12 = nn12; ma.n_src = n_src; ma.n_tgt = n_tgt; ma.Nmax = Nmax; ma.Mmax = Mmax;
-    ma.mutual = mutual; ma.ransac_n = ransac_n; ma.Kt = 16 * v.NX; ma.D = D; ma.ntm = ntm;
-    ma.v12 = v12; ma.e12 = e12; ma.wq = wq; ma.fmax = v.fmax;
-    ma.nns = v.S <= 2 ? nns : nn12;  // featnn_row7 (S > 2) writes no copy
+    ma.mutual = mutual; ma.ransac_n = ransac_n; ma.Kt = 16 * v.NX; ma.D = D; ma.ntm = g.nt;
+    ma.v12 = o1.v; ma.e12 = o1.e; ma.wq = o2.wq; ma.fmax = f.nmax;
+    ma.nns = v.S <= 2 ? o1.nns : nn12;  // featnn_row7 (S > 2) writes no copy
     ma.F = F; ma.G = G; ma.mx = v.mx;
     ma.list21 = v.list21; ma.cnt21 = v.cnt21; ma.nn21x = nn21x;
     ma.corres = corres; ma.n_corres = n_corres;
-    // pass 1: F rows x all G columns (nrb: each launcher sets its own)
-    RowArgs5 r;
-    r.Ap = v.Ap; r.Bp = v.Bp; r.ich = v.ich; r.rnr = v.fnr; r.cmax = v.gmax; r.n_rows = n_src; r.n_cols = n_tgt;
-    r.rlist = nullptr; r.rcount = nullptr; r.P = P; r.Rmax = Nmax; r.Cmax = Mmax; r.ntr = ntn;
-    r.ntc = ntm; r.nrb = 0; r.D = D; r.ctbits = 1;
-    while ((1 << r.ctbits) < ntm) ++r.ctbits;
-    r.nn = nn12; r.v = v12; r.e = e12;
-    // a 1-term screen lists the rows it leaves to the 3-term one
-    r.list = one ? v.fbl12 : v.list12; r.count = one ? v.fbc12 : v.cnt12;
-    r.wq = nullptr;
-    r.Xr = F; r.sc = v.mx; r.role = 0; r.cs = v.sp.cs;  // featnn_row8 builds its rows from F
-    r.cemax = v.gemax; r.nns = nns; r.fbdiag = 0; r.rbmajor = 0;
-    r.rre = v.fre; r.bcnt = bcnt; r.blist = blist; r.bcap = cap1; r.rec = rec;
-    r.cct = v.gct; r.rct = v.fct; r.cbias = v.cbias;
-    r.csl = 1; r.part = part; r.llist = nullptr; r.lcount = nullptr;
-    r.thresh = 0; r.cand = cand; r.used = nullptr; r.Xc = G; r.fbctr = nullptr; r.dbg = 0;
     auto prep_hook = [&](int at) -> int {
         if (!prep_event || prep_at != at) return PCR_OK;
         PCR_HIP_CHECK(hipEventRecord(prep_event, s));
@@ -444,22 +418,14 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
         return hrc;
     };
     if ((rc = prep_hook(2)) != PCR_OK) return rc;
-    // (the regroup's failing rows go to the exact rescan's list: the 3-term screen runs beside it)
-    // the threshold route's view of a pass: the rows r lists; what it leaves goes to list / count
-    auto thresh_args = [](RowArgs5 t, int *list, int *count) {
-        t.rlist = t.list; t.rcount = t.count;
-        t.llist = list; t.lcount = count;
-        return t;
-    };
-    const RowArgs5 t1 = thresh_args(r, v.list12, v.cnt12);
-    rc = run_pass<true>(r, fallback_args(r, v.list12, v.cnt12, 1, fsl), v.S, one, use9, kProfFeatScreen,
-                        kProfFeatScreen1b, v.list12, v.cnt12, s, thresh ? &t1 : nullptr);
+    // pass 1: F rows x all G columns
+    rc = run_pass<true>(rt, make_pass(screen_args(v, 0, rt, o1), 0, rt, v.list12, v.cnt12), s);
     if (rc != PCR_OK) return rc;
     if ((rc = prep_hook(1)) != PCR_OK) return rc;
     RescanArgs5 ra = rescan_args(F, G, n_src, n_tgt, Nmax, Mmax, D);
     ra.list12 = v.list12; ra.list21 = v.list21; ra.cnt12 = v.cnt12; ra.cnt21 = zero;
     ra.nn12 = nn12; ra.nn21 = nn21x;
-    ra.v12 = v12; ra.e12 = e12; ra.mx = v.mx; ra.T = v.sp.T;
+    ra.v12 = o1.v; ra.e12 = o1.e; ra.mx = v.mx; ra.T = v.sp.T;
     // mutual: the exact rescan of the uncertified rows runs on a side stream
     // beside J's build and pass 2, which read none of its results (J from the
     // screened argmins; featmut_resolve, after the join, sends a rescanned
@@ -495,26 +461,11 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
         }
         PCR_LAUNCH_CHECK();
         // pass 2: the rows J of G (B-role fragments as the register operand) x all F
-        // columns (A-role fragments streamed): the same products, values only
-        RowArgs5 r2 = r;
-        r2.Ap = v.Bp; r2.Bp = v.Ap; r2.rnr = v.gnr; r2.cmax = v.fmax; r2.n_rows = n_tgt;
-        r2.n_cols = n_src; r2.rlist = ma.jlist; r2.rcount = ma.nj; r2.Rmax = Mmax; r2.Cmax = Nmax;
-        r2.ntr = ntm; r2.ntc = ntn;
-        r2.nn = nullptr; r2.v = nullptr; r2.e = nullptr;
-        // values only; the columns whose gap the 1-term screen cannot use go to the 3-term
-        r2.list = one ? v.fbl21 : nullptr; r2.count = one ? v.fbc21 : nullptr;
-        r2.nns = nullptr;
-        r2.wq = wq;
-        r2.Xr = G; r2.sc = v.mx; r2.role = 1; r2.cs = v.sp.cs;
-        r2.cemax = v.femax;
-        const RowArgs5 r2b = fallback_args(r2, nullptr, nullptr, 2, fsl);
-        if (use9) { r2.rre = v.gre; r2.bcap = cap2; r2.cct = v.fct; r2.rct = v.gct; }
-        // (no list for the finish: the resolve sends an undecided column to the exact column rescan)
-        // (the threshold route: the exact argmin of a settled column goes to nn21x, its flag to 2)
-        RowArgs5 t2 = thresh_args(r2, nullptr, nullptr);
-        t2.nn = nn21x; t2.used = ma.used; t2.Xc = F;
-        rc = run_pass<false>(r2, r2b, v.S, one, use9, kProfFeatScreen2, kProfFeatScreen2b, nullptr, nullptr, s,
-                             thresh ? &t2 : nullptr);
+        // columns (A-role fragments streamed): the same products, values only.  The
+        // threshold route writes a settled column's exact argmin to nn21x, its flag to 2
+        Pass p2 = make_pass(screen_args(v, 1, rt, o2), 1, rt, nullptr, nullptr);
+        p2.th.nn = nn21x; p2.th.used = ma.used;
+        rc = run_pass<false>(rt, p2, s);
         if (rc != PCR_OK) return rc;
         if (rs != s) PCR_HIP_CHECK(hipStreamWaitEvent(s, ev_join, 0));
         hipLaunchKernelGGL(featmut_resolve, dim3(cdiv(Nmax, 256), P), dim3(256), 0, s, ma);
@@ -606,8 +557,7 @@ extern "C" int pcr_feature_correspondences(const float *src_feat, const float *t
                                     ransac_n, nn12, corres, n_corres, s);
 }
 
-// debug: copy the mutual path's scratch (v12 | e12 | wq (16-B aligned) | used | pos | jlist |
-// nn21x | flag | nj, feature_corres_v5's layout) of the last call to dst
+// debug: copy the mutual path's scratch (feature_corres_v5's layout) of the last call to dst
 extern "C" int pcr_featmut_debug_copy(void *dst, int64_t bytes, pcr_stream_t stream) {
     pcr::clear_error();
     void *src = pcr::workspace(pcr::kWsFeatMutual, 16);

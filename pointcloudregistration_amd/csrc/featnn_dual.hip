@@ -267,10 +267,11 @@ int feature_match_v5(const float *F, const float *G, int P, int Nmax, int Mmax, 
     int rc = v5_prepare(F, G, P, Nmax, Mmax, D, n_src, n_tgt, s, v);
     if (rc != PCR_OK) return rc;
     PCR_REQUIRE(v.ich == v.NM, PCR_ERR_ARG, "feature_match: the dual screen needs the full operand image");
-    const int W = v.W, nrb = v.nrb, ntm = v.ntm;
+    const V5Side &f = v.side[0], &g = v.side[1];
+    const int W = v.W, nrb = v.nrb, ntm = g.nt;
     DualArgs5 d;
-    d.Ap = v.Ap; d.Bp = v.Bp; d.fnr = v.fnr; d.gnr = v.gnr; d.fmax = v.fmax; d.gmax = v.gmax;
-    d.n_src = n_src; d.n_tgt = n_tgt; d.P = P; d.Nmax = Nmax; d.Mmax = Mmax; d.ntn = v.ntn;
+    d.Ap = f.Xp; d.Bp = g.Xp; d.fnr = f.nr; d.gnr = g.nr; d.fmax = f.nmax; d.gmax = g.nmax;
+    d.n_src = n_src; d.n_tgt = n_tgt; d.P = P; d.Nmax = Nmax; d.Mmax = Mmax; d.ntn = f.nt;
     d.ntm = ntm; d.nrb = nrb; d.D = D; d.nn12 = nn12; d.list12 = v.list12;
     d.count12 = v.cnt12;
     // the dual screen's row code: column tiles only

@@ -528,6 +528,8 @@ int g_image_chunks = 0;
 
 int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D, const int32_t *n_src,
                const int32_t *n_tgt, hipStream_t s, V5Buf &v, bool compact) {
+    v.P = P;
+    v.D = D;
     v.S = cdiv(D, 16);
     v.NM = 2 * v.S + 1;
     v.ich = compact ? v.S : v.NM;
@@ -536,29 +538,29 @@ int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
     v.sp = split5_params(D);
     v.W = 8;                                          // waves (32-row tiles) per workgroup
     v.nrb = cdiv(cdiv(Nmax, 32), v.W);                // dual screen row blocks
-    // row tiles, padded to whole blocks of the dual screen (8 tiles) and of the
-    // row screens (8 waves x up to 2 tiles; the sentinel rows are valid encodings)
-    v.ntn = cdiv(cdiv(Nmax, 32), 16) * 16;
-    v.ntm = cdiv(cdiv(Mmax, 32), std::max(kRow8G, kRow9G)) * std::max(kRow8G, kRow9G);  // column tiles, whole groups
+    const FeatTiles tiles = feat_tiles(Nmax, Mmax);
+    const int ich = v.ich, ntn = tiles.ntn, ntm = tiles.ntm;
+    V5Side &f = v.side[0], &g = v.side[1];
+    f.X = F; f.n = n_src; f.Nmax = Nmax; f.nt = ntn;
+    g.X = G; g.n = n_tgt; g.Nmax = Mmax; g.nt = ntm;
     v.ctbits = 1;
-    while ((1 << v.ctbits) < std::max(v.ntm, v.ntn)) ++v.ctbits;
+    while ((1 << v.ctbits) < std::max(ntm, ntn)) ++v.ctbits;
     PCR_REQUIRE(v.ctbits <= 16, PCR_ERR_ARG, "feature_match: N=%d / M=%d too large", Nmax, Mmax);
-    const int ich = v.ich, ntn = v.ntn, ntm = v.ntm;
     const size_t ap = (size_t)P * ntn * ich * 64, bp = (size_t)P * ntm * ich * 64;  // f16x8
     const size_t nn_n = (size_t)P * ntn * 32, nn_m = (size_t)P * ntm * 32;
     const size_t pn = (size_t)P * Nmax, pm = (size_t)P * Mmax;
     unsigned *mxp, *smax;
     int *bad;
     WsLayout l;
-    l.take(v.Ap, ap); l.take(v.Bp, bp);
-    l.take(v.fnr, nn_n); l.take(v.gnr, nn_m);
-    l.take(v.fre, nn_n); l.take(v.gre, nn_m);
-    l.take(v.fct, nn_n); l.take(v.gct, nn_m);
-    // nine [P] arrays, contiguous from gmax: max|y|, max|x|, the scale used, cnt12, cnt21,
-    // gemax, femax, fbc12, fbc21 (feat_sample clears all but the scale)
-    l.take(v.gmax, P); l.take(v.fmax, P); l.take(v.mx, P);
+    l.take(f.Xp, ap); l.take(g.Xp, bp);
+    l.take(f.nr, nn_n); l.take(g.nr, nn_m);
+    l.take(f.re, nn_n); l.take(g.re, nn_m);
+    l.take(f.ct, nn_n); l.take(g.ct, nn_m);
+    // nine [P] arrays, contiguous from G's max norm: max|y|, max|x|, the scale used, cnt12,
+    // cnt21, G's and F's max split error, fbc12, fbc21 (feat_sample clears all but the scale)
+    l.take(g.nmax, P); l.take(f.nmax, P); l.take(v.mx, P);
     l.take(v.cnt12, P); l.take(v.cnt21, P);
-    l.take(v.gemax, P); l.take(v.femax, P);
+    l.take(g.emax, P); l.take(f.emax, P);
     l.take(v.fbc12, P); l.take(v.fbc21, P);
     l.take(v.list12, pn); l.take(v.list21, pm);  // per pair, stride Nmax / Mmax
     l.take(v.fbl12, pn); l.take(v.fbl21, pm);    // per pair, stride Nmax / Mmax
@@ -569,21 +571,21 @@ int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
     PCR_REQUIRE(workspace_bind(kWsFeatPack_NndRagged, l, kWsSlack), PCR_ERR_NOMEM, "feature_match: %s",
                 pcr_last_error());
     prof_begin(s, kProfFeatPack);
-    hipLaunchKernelGGL(feat_sample, dim3(P), dim3(256), 0, s, F, n_src, Nmax, G, n_tgt, Mmax, D, smax, v.gmax,
+    hipLaunchKernelGGL(feat_sample, dim3(P), dim3(256), 0, s, F, n_src, Nmax, G, n_tgt, Mmax, D, smax, g.nmax,
                        bad, P);
     PCR_LAUNCH_CHECK();
+    const PackIO io{{f.X, g.X},   {f.n, g.n},       {f.Nmax, g.Nmax}, {f.nt, g.nt}, {f.Xp, g.Xp},
+                    {f.nr, g.nr}, {f.nmax, g.nmax}, {f.emax, g.emax}, {f.re, g.re}, {f.ct, g.ct}};
     // the repair passes: few blocks walking the flags (empty in the common case)
     const int R = std::min(P, kRepairR), zr = 8;
     for (int rep = 0; rep < 2; ++rep) {
         PackCtl pc{smax, mxp, zr, P, rep, bad, v.mx};
         if (rep) {
             hipLaunchKernelGGL(feat_maxabs, dim3(R, 2, zr), dim3(1024), 0, s, F, n_src, Nmax, G, n_tgt, Mmax, D,
-                               mxp, v.gmax, bad, P);
+                               mxp, g.nmax, bad, P);
             PCR_LAUNCH_CHECK();
         }
         const int gy = rep ? R : P;
-        PackIO io{{F, G}, {n_src, n_tgt}, {Nmax, Mmax}, {ntn, ntm}, {v.Ap, v.Bp}, {v.fnr, v.gnr}, {v.fmax, v.gmax},
-                  {v.femax, v.gemax}, {v.fre, v.gre}, {v.fct, v.gct}};
         const dim3 grid(cdiv(std::max(ntn, ntm), 4), gy, 2);
         // (the repair launch stores the layout of the first)
         static_assert(kRow8G % 8 == 0, "feat_pack5c: whole blocks of eight tiles");
@@ -593,8 +595,8 @@ int v5_prepare(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
         else hipLaunchKernelGGL(feat_pack5, grid, dim3(256), 0, s, io, D, v.S, ich, v.sp, pc);
         PCR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(feat_colterms, dim3(cdiv(std::max(ntn, ntm) * 32, 256), P, 2), dim3(256), 0, s, v.fct, v.gct,
-                       ntn, ntm, v.fmax, v.gmax, v.femax, v.gemax, v.cbias);
+    hipLaunchKernelGGL(feat_colterms, dim3(cdiv(std::max(ntn, ntm) * 32, 256), P, 2), dim3(256), 0, s, f.ct, g.ct,
+                       ntn, ntm, f.nmax, g.nmax, f.emax, g.emax, v.cbias);
     PCR_LAUNCH_CHECK();
     prof_end(s, kProfFeatPack);
     return PCR_OK;

@@ -1,8 +1,11 @@
 // The f16 x3 split feature screen (D <= 64), shared by its units: the operand
-// layout, the certification bounds, the kernels' argument structs and the host
-// entry points that cross units (featnn.hip has the map of the units).
+// layout, the certification bounds, the kernels' argument structs (their layout
+// is the kernels' ABI), the per-cloud view of the packed workspace (V5Side,
+// V5Buf) and the host entry points that cross units (featnn.hip has the map of
+// the units; featnn_route.h the route's constants and the tile padding).
 #pragma once
 #include "featnn_common.h"
+#include "featnn_route.h"
 
 namespace pcr {
 
@@ -126,17 +129,6 @@ struct DualArgs5 {
     int *cpi;
 };
 
-// column tiles per LDS group of featnn_row8 / featnn_row9 (v5_prepare pads the
-// column images to whole groups of both)
-constexpr int kRow8G = 8;      // column tiles per LDS group (16: the whole LDS, measured no faster)
-#ifndef PCR_ROW9_G
-#define PCR_ROW9_G 16  // 8: pass 1 1.12 vs 1.09 ms, pass 2 0.76 vs 0.74 (C4, featnn_bench)
-#endif
-#ifndef PCR_ROW9_G1
-#define PCR_ROW9_G1 PCR_ROW9_G
-#endif
-constexpr int kRow9G = PCR_ROW9_G;     // featnn_row9's: pass 2 (and the padding)
-constexpr int kRow9G1 = PCR_ROW9_G1;   // pass 1 (<= kRow9G)
 // B: pass 1 1.0 (row k = 6) x 2^15 (G's column image, k = 6); pass 2 (featnn_row8
 // <.., false>, the J rows of G against F's image) 1.0 (row k = 7) x 2^15 (F's
 // image, k = 7).  dual7 pairs F's image with G's: 0 x 2^15 at both slots.
@@ -229,47 +221,60 @@ struct RescanArgs5 {
     int T;
 };
 
-// the row screens' arguments (the mutual path: feature_corres_v5 in featnn.hip)
+// The row screens' arguments (the mutual path, featnn.hip).  Every field has a
+// default, and the screen of a pass is filled in one place (screen_args there);
+// the other kernels take views of it that re-point three (list, count) pairs:
+//                      rlist / rcount         list / count            llist / lcount
+//   featnn_row7/8/9    pass 2: the rows J     rows left uncertified   -
+//   featnn_regroup9    -                      -                       -
+//   featnn_finish9     -                      -                       its failing rows
+//   featnn_row8 list,  the screen's list      rows left uncertified   -
+//    featnn_slicemerge                        (to the exact rescan)
+//   featnn_thresh9,    the screen's list      -                       rows left unsettled
+//    featnn_exact_cand                                                (to the exact rescan)
+// A null list drops the rows (pass 2: featmut_resolve sends an undecided column to
+// the exact column rescan).  With thresh = 1 the finish's llist is the screen's
+// own list: it appends to what the sweep listed.
 struct RowArgs5 {
-    const f16x8 *Ap;            // row operand (register-resident): [P][ntr][ich][64]
-    const f16x8 *Bp;            // column operand (LDS-streamed): [P][ntc][ich][64]
-    int ich;                    // stored chunks per tile of both images: NM, or S (compact: the hi segment only)
-    const float *rnr;           // scaled row norms, [P][ntr * 32] by original row index
-    const unsigned *cmax;       // per pair max scaled column norm (f32 bits)
-    const int32_t *n_rows, *n_cols;
-    const int *rlist, *rcount;  // pass 2: rows rlist[p][0 .. rcount[p]) (original indices)
-    int P, Rmax, Cmax, ntr, ntc, nrb, D, ctbits;
-    int32_t *nn;                // pass 1: argmin (screened), value, its error, uncertified rows
-    double *v;
-    float *e;
-    int *list, *count;
-    float4 *wq;                 // pass 2: (top-2 values, the screen's error bound, -) by original row index
+    const f16x8 *Ap = nullptr;  // row operand (register-resident): [P][ntr][ich][64]
+    const f16x8 *Bp = nullptr;  // column operand (LDS-streamed): [P][ntc][ich][64]
+    int ich = 0;                // stored chunks per tile of both images: NM, or S (compact: the hi segment only)
+    const float *rnr = nullptr;      // scaled row norms, [P][ntr * 32] by original row index
+    const unsigned *cmax = nullptr;  // per pair max scaled column norm (f32 bits)
+    const int32_t *n_rows = nullptr, *n_cols = nullptr;
+    const int *rlist = nullptr, *rcount = nullptr;  // pass 2: rows rlist[p][0 .. rcount[p]) (original indices)
+    int P = 0, Rmax = 0, Cmax = 0, ntr = 0, ntc = 0, nrb = 0, D = 0, ctbits = 0;
+    int32_t *nn = nullptr;      // pass 1: argmin (screened), value, its error, uncertified rows
+    double *v = nullptr;
+    float *e = nullptr;
+    int *list = nullptr, *count = nullptr;
+    float4 *wq = nullptr;       // pass 2: (top-2 values, the screen's error bound, -) by original row index
     // pass 2: the gathered rows built in registers from the f32 cloud (one
     // 128-byte row per lane instead of ten 16-byte pieces in ten lines of the
     // packed image), with the scale the packs used and the image's role
-    const float *Xr;
-    const unsigned *sc;
-    int role, cs;
-    const unsigned *cemax;      // featnn_row8<.., kOne>: per pair max |y - f16(y)| of the column image
-    int32_t *nns;               // pass 1: a copy of the screened argmin for featmut_jbuild (nullable)
-    int fbdiag;                 // 1 / 2: count the listed rows in g_featnn_fallback_rows[0 / 1]
-    int rbmajor;                // featnn_row8: blocks ordered row block first (short lists, below)
-    const float *rre;           // the rows' |x - f16(x)| from the pack, [P][ntr * 32]
+    const float *Xr = nullptr;
+    const unsigned *sc = nullptr;
+    int role = 0, cs = 0;
+    const unsigned *cemax = nullptr;  // featnn_row8<.., kOne>: per pair max |y - f16(y)| of the column image
+    int32_t *nns = nullptr;     // pass 1: a copy of the screened argmin for featmut_jbuild (nullable)
+    int fbdiag = 0;             // 1 / 2: count the listed rows in g_featnn_fallback_rows[0 / 1]
+    int rbmajor = 0;            // featnn_row8: blocks ordered row block first (short lists, below)
+    const float *rre = nullptr; // the rows' |x - f16(x)| from the pack, [P][ntr * 32]
     // featnn_row9's buckets (rows by winning step): [P][steps] counts and
     // [P][steps][bcap] entries (row, B1, B2, lane half of the winning group)
-    int *bcnt, bcap;
-    uint4 *blist;
-    uint4 *rec;                 // featnn_regroup9 -> featnn_finish9, by row: (column, B1, B2, skip)
-    int *llist, *lcount;        // featnn_finish9: where its failing rows go (nullable)
+    int *bcnt = nullptr, bcap = 0;
+    uint4 *blist = nullptr;
+    uint4 *rec = nullptr;       // featnn_regroup9 -> featnn_finish9, by row: (column, B1, B2, skip)
+    int *llist = nullptr, *lcount = nullptr;  // featnn_finish9: where its failing rows go (nullable)
     // featnn_row8 list mode over column slices (csl > 1: short lists at small
     // batches): slice sl's partial (B1, B2, column) per listed row position k,
     // [P][csl][Rmax], merged by featnn_slicemerge
-    int csl;
-    uint4 *part;
+    int csl = 0;
+    uint4 *part = nullptr;
     // featnn_row9: the column cloud's and the row cloud's per-row terms
     // f32(|.|^2 + B) ([P][ntc * 32], [P][ntr * 32]) and B
-    const float *cct, *rct;
-    const float *cbias;  // [P] B
+    const float *cct = nullptr, *rct = nullptr;
+    const float *cbias = nullptr;  // [P] B
     // the threshold route (featnn_thresh.hip): thresh = 1 makes featnn_finish9
     // re-mark the rows it lists as the sweep marks its own, rec = (0, B1,
     // 0xffffffff, 1) -- featnn_thresh9's candidate counter, the row's smallest
@@ -277,11 +282,11 @@ struct RowArgs5 {
     // [kThreshK] candidate columns; used: featmut's column flags (pass 2);
     // Xc: the column cloud (f32); fbctr: g_featnn_fallback_rows; dbg:
     // featnn_exact_cand keeps statistics
-    int thresh;
-    int *cand, *used;
-    const float *Xc;
-    unsigned long long *fbctr;
-    int dbg;
+    int thresh = 0;
+    int *cand = nullptr, *used = nullptr;
+    const float *Xc = nullptr;
+    unsigned long long *fbctr = nullptr;
+    int dbg = 0;
 };
 
 namespace {
@@ -361,21 +366,31 @@ __device__ __forceinline__ double row_bound_ct(const RowArgs5 &a, int p, int row
 
 }  // namespace
 
+// what the pack produces for one cloud, and what addresses it
+struct V5Side {
+    const float *X;    // the f32 cloud, [P][Nmax][D]
+    const int32_t *n;  // [P] counts (null: Nmax each)
+    int Nmax, nt;      // rows per pair; 32-row tiles per pair as padded (feat_tiles)
+    f16x8 *Xp;         // packed image, [P][nt][ich][64]
+    float *nr;         // per row scaled norm, [P][nt * 32]
+    unsigned *nmax;    // [P] max scaled norm (f32 bits)
+    unsigned *emax;    // [P] max |x - f16(x)| (the 1-term screens' bound)
+    float *re;         // per row |x - f16(x)| (scaled, rounded up)
+    float *ct;         // per row f32(|x|^2 + B) (featnn_row9's column terms)
+};
+
 // packed operands, norms and per-pair maxima of both clouds (shared by the
-// dual screen and the mutual path)
+// dual screen and the mutual path): side 0 = F (the sources), 1 = G (the targets)
 struct V5Buf {
-    int S, NM, NX, W, nrb, ntn, ntm, ctbits;  // S chunks per D-segment, NM stored, NX executed
+    int P, D;
+    int S, NM, NX, W, nrb, ctbits;  // S chunks per D-segment, NM stored, NX executed
     int ich;  // chunks per tile the images hold: NM, or S when compact (v5_prepare)
     Split5 sp;
-    f16x8 *Ap, *Bp;
-    float *fnr, *gnr;
-    unsigned *gmax, *fmax, *mx;
+    V5Side side[2];
+    unsigned *mx;                        // [P] the scale the packs used (f32 bits)
     int *cnt12, *cnt21, *list12, *list21;
-    unsigned *gemax, *femax;  // per pair max |x - f16(x)| of the column (G) / row (F) images
     int *fbc12, *fbc21, *fbl12, *fbl21;  // the rows a 1-term screen left for the 3-term one
-    float *fre, *gre;                    // per row |x - f16(x)| of F / G (scaled, rounded up)
-    float *fct, *gct;                    // per row f32(|x|^2 + B) of F / G (featnn_row9's column terms)
-    float *cbias;                        // [P] their B (feat_colterms)
+    float *cbias;                        // [P] the column terms' B (feat_colterms)
 };
 
 // featnn_pack.hip; compact: the images hold the hi segment only (S chunks per
@@ -390,7 +405,6 @@ RescanArgs5 rescan_args(const float *F, const float *G, const int32_t *n_src, co
                         int Mmax, int D);
 int run_rescan(RescanArgs5 &ra, int P, int D, hipStream_t s);
 // featnn_row.hip (instantiated there for every kIdx / kOne); each sets its own r.nrb
-constexpr int kRegroupMaxSteps = 4096;  // featnn_regroup9 keeps a pair's per-step prefix in LDS
 template <bool kIdx> int launch_row7(const RowArgs5 &r, int S, hipStream_t s);  // S = 3, 4
 template <bool kIdx, bool kOne> int launch_row8(const RowArgs5 &r, int S, hipStream_t s);
 template <bool kIdx> int launch_row9(const RowArgs5 &r, int S, hipStream_t s);

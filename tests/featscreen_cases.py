@@ -14,6 +14,33 @@ K_SAMPLE_ROWS = 64
 K_SPEC_MARGIN = 1
 
 
+def mut_scratch(P, Nmax, Mmax):
+    """Named views of the scratch of the last pcr_feature_correspondences call at
+    D <= 64, read through pcr_featmut_debug_copy (needs the GPU).  The one copy of
+    feature_corres_v5's layout (csrc/featnn.hip) on the test side: each array at
+    the next multiple of its element's alignment, in the order of its take()s --
+      v12 [P][Nmax] f64, e12 [P][Nmax] f32, wq [P][Mmax][4] f32 (16-byte aligned),
+      used, pos [P][Mmax + 1] i32, jlist, nn21x [P][Mmax] i32, flag [P][Nmax + 1]
+      i32, nj [P] i32.
+    used / pos / flag keep their per-pair extra element."""
+    import torch
+    from pointcloudregistration_amd import _lib
+    fields = (("v12", np.float64, (P, Nmax), 8), ("e12", np.float32, (P, Nmax), 4),
+              ("wq", np.float32, (P, Mmax, 4), 16), ("used", np.int32, (P, Mmax + 1), 4),
+              ("pos", np.int32, (P, Mmax + 1), 4), ("jlist", np.int32, (P, Mmax), 4),
+              ("nn21x", np.int32, (P, Mmax), 4), ("flag", np.int32, (P, Nmax + 1), 4), ("nj", np.int32, (P,), 4))
+    at, end = {}, 0
+    for name, dt, shape, align in fields:
+        at[name] = (end + align - 1) // align * align
+        end = at[name] + int(np.prod(shape)) * np.dtype(dt).itemsize
+    buf = torch.empty(end, dtype=torch.uint8, device="cuda")
+    _lib.call("pcr_featmut_debug_copy", buf.data_ptr(), buf.numel(), _lib.stream_handle())
+    torch.cuda.synchronize()
+    raw = buf.cpu().numpy()
+    return {name: raw[at[name]:at[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape)
+            for name, dt, shape, align in fields}
+
+
 def split5_params(D):
     L = 0
     while (1 << L) < D:

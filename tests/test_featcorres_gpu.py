@@ -11,6 +11,7 @@ screen (ties, duplicates, NaN rows, 9-decade ranges, offsets, subnormals)."""
 import numpy as np
 import pytest
 
+import featscreen_cases as fc
 from pointcloudregistration_amd import registration as reg
 from pointcloudregistration_amd import synth
 
@@ -211,46 +212,11 @@ def test_feature_correspondences_three_term_only(oracle, monkeypatch, name):
     assert np.array_equal(_np(co)[0, :len(exp)], exp)
 
 
-def _used_flags(P, Nmax, Mmax):
-    """featmut_jbuild / featmut_resolve's per-column flags of the last
-    pcr_feature_correspondences call (its scratch, pcr_featmut_debug_copy):
-    [P][Mmax + 1] ints after v12 (f64) | e12 (f32) | wq (float4, 16-aligned)."""
-    import torch
-    from pointcloudregistration_amd import _lib
-    off = ((12 * P * Nmax + 15) // 16) * 16 + 16 * P * Mmax
-    n = P * (Mmax + 1)
-    buf = torch.empty(off + 4 * n, dtype=torch.uint8, device="cuda")
-    _lib.call("pcr_featmut_debug_copy", buf.data_ptr(), buf.numel(), _lib.stream_handle())
-    torch.cuda.synchronize()
-    return _np(buf[off:].view(torch.int32)).reshape(P, Mmax + 1)
-
-
 # featmut_jbuild / featmut_resolve's per-column flags
 USED_NONE = 0      # no row picked the column: pass 2 did not screen it
 USED_SCREENED = 1  # in J: pass 2 screened it, wq decided its candidates
 USED_RESCAN = 2    # in J and screened (wq valid), but listed for the exact column rescan
 USED_OUTSIDE = 3   # a rescanned row's exact argmin outside J: rescanned, never screened (no wq)
-
-
-def _mut_scratch(P, Nmax, Mmax):
-    """v12 [P][Nmax] f64, e12 [P][Nmax] f32, wq [P][Mmax][4] f32, used [P][Mmax]
-    of the last pcr_feature_correspondences call (feature_corres_v5's scratch:
-    v12 | e12 | wq (16-byte aligned) | used [P][Mmax + 1] | ...)."""
-    import torch
-    from pointcloudregistration_amd import _lib
-    pn, pm = P * Nmax, P * Mmax
-    o_wq = ((12 * pn + 15) // 16) * 16
-    o_used = o_wq + 16 * pm
-    total = o_used + 4 * P * (Mmax + 1)
-    buf = torch.empty(total, dtype=torch.uint8, device="cuda")
-    _lib.call("pcr_featmut_debug_copy", buf.data_ptr(), buf.numel(), _lib.stream_handle())
-    torch.cuda.synchronize()
-    raw = _np(buf)
-    v12 = raw[:8 * pn].view(np.float64).reshape(P, Nmax)
-    e12 = raw[8 * pn:12 * pn].view(np.float32).reshape(P, Nmax)
-    wq = raw[o_wq:o_used].view(np.float32).reshape(P, Mmax, 4)
-    used = raw[o_used:total].view(np.int32).reshape(P, Mmax + 1)[:, :Mmax]
-    return v12, e12, wq, used
 
 
 @pytest.mark.parametrize("P", [1, 192])
@@ -270,7 +236,7 @@ def test_resolve_outside_j(oracle, P):
         tw = np.repeat(fs[p], 2, axis=0) + (rng.standard_normal((2 * N, D)) * 1e-6).astype(np.float32)
         ft[p] = np.concatenate([tw, rng.standard_normal((K, D)).astype(np.float32)])[rng.permutation(M)]
     co, nc, nn12 = reg.feature_correspondences(fs, ft)
-    used = _used_flags(P, N, M)
+    used = fc.mut_scratch(P, N, M)["used"]
     outside = (used[:, :M] == 3).sum(axis=1)
     assert outside.min() > 0, outside
     nn12, nc, co = _np(nn12), _np(nc), _np(co)

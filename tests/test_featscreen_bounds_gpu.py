@@ -3,8 +3,8 @@
 row_tail (csrc/featnn_row.hip) stores for every pass-1 row its screened value and an
 error bound, v12 / e12, and for every pass-2 column wq = (w1 + bias, w2 + bias,
 e2, bias); featmut_resolve decides mutuality from these numbers alone.  Here
-they are read back (pcr_featmut_debug_copy, the layout of feature_corres_v5's
-scratch) and each CLAIM is checked: |value - s^2 D_exact| <= its bound, with
+they are read back (featscreen_cases.mut_scratch: feature_corres_v5's scratch
+through pcr_featmut_debug_copy) and each CLAIM is checked: |value - s^2 D_exact| <= its bound, with
 D_exact in f64 from the f32 inputs and s the pair's power-of-two scale (x s is
 exact), recovered from the values themselves.  The only slack is the f64
 rounding of the reference, 1e-12 s^2 (|x|^2 + |y|^2) (D 2^-52 relative with a
@@ -20,7 +20,7 @@ import pytest
 
 import featscreen_cases as fc
 from pointcloudregistration_amd import registration as reg
-from test_featcorres_gpu import CASES, USED_RESCAN, USED_SCREENED, _mut_scratch
+from test_featcorres_gpu import CASES, USED_RESCAN, USED_SCREENED
 
 pytestmark = pytest.mark.gpu
 
@@ -119,7 +119,8 @@ def test_certificates_hold(monkeypatch, name, path):
     F, G = ALL[name]
     P, N, M = F.shape[0], F.shape[1], G.shape[1]
     co, nc, nn12 = reg.feature_correspondences(F, G)
-    v12, e12, wq, used = _mut_scratch(P, N, M)
+    sc = fc.mut_scratch(P, N, M)
+    v12, e12, wq, used = sc["v12"], sc["e12"], sc["wq"], sc["used"][:, :M]
     nn12 = _np(nn12)
     for p in range(P):
         s2, D = _check_pair(name, p, nn12[p], v12[p], e12[p], wq[p], used[p])

@@ -9,7 +9,9 @@ oracle's corres(featnn(F, G), featnn(G, F)), and the 3-term route
 (PCR_FEAT_THRESH=0) gives identical outputs.  Shapes: counts in {1, 31, 33,
 257} (one column tile and a lane short of it, one over, several row tiles and
 column steps), ragged, D in {16, 17, 32}, 1 and 9 pairs (9: the p mod 8 XCD
-map, and more than one column slice per row tile at a 64-wave pair).
+map, and more than one column slice per row tile at a 64-wave pair); and on
+every route of the driver (each PCR_FEAT_* hook, S = 3) clouds of 513 x 257 and
+257 x 513 rows, which pad to different tile counts.
 
 The CPU tests need no GPU: a numpy model of the screen's candidate sets (how
 many columns fall within a row's threshold, so the twin inputs are known to
@@ -187,6 +189,73 @@ def test_random_descriptors_ragged(oracle, monkeypatch, D, counts):
     if counts:
         ns, nt = (np.array(c, np.int32) for c in COUNTS[counts])
     _check(oracle, monkeypatch, ("random", D, counts), F, G, ns, nt)
+
+
+ROUTES = {  # (D, the hook, stored chunks per image tile): every route of feature_corres_v5
+    "default": (32, None, 2),
+    "image_full": (32, ("PCR_FEAT_IMAGE", "full"), 5),
+    "three_term_leftovers": (32, ("PCR_FEAT_THRESH", "0"), 5),
+    "row8_one_term": (32, ("PCR_FEAT_ROW9", "0"), 5),
+    "three_term_only": (32, ("PCR_FEAT_ONE", "0"), 5),
+    "row7_s3": (48, None, 7),
+}
+
+
+def _unequal_sides(D, wide_src):
+    """Four pairs whose clouds pad to different tile counts: per-pair counts from
+    {1, 33, 513} on one side (Nmax 513: 17 row tiles, padded to 32) and {31, 65,
+    257} on the other (Mmax 257: 9 tiles, padded to 16), the last pair empty on
+    the wide side; wide_src: the wide side is the sources.  Noisy copies of a
+    code book with a quarter of each cloud twinned 1e-2 away (rows and J
+    columns the 1-term certificate fails).  Past a pair's count each cloud holds
+    exact copies of the other's rows: as an argmin they would win."""
+    key = ("unequal", D, wide_src)
+    if key not in _MEMO:
+        rng = np.random.default_rng(1700 + D + wide_src)
+        P, nw, nn = 4, 513, 257
+        code = rng.standard_normal((P, 560, D)).astype(np.float32)
+        W = (np.stack([code[p, rng.permutation(560)[:nw]] for p in range(P)]) +
+             rng.normal(0, 0.6, (P, nw, D))).astype(np.float32)
+        N = (np.stack([code[p, rng.permutation(560)[:nn]] for p in range(P)]) +
+             rng.normal(0, 0.6, (P, nn, D))).astype(np.float32)
+        cw, cn = np.array([513, 1, 33, 0], np.int32), np.array([31, 257, 65, 100], np.int32)
+        for X, c in ((W, cw), (N, cn)):
+            for p in range(P):
+                k = int(c[p]) // 4
+                idx = rng.permutation(int(c[p]))[:2 * k]
+                X[p, idx[k:]] = X[p, idx[:k]] + (1e-2 * rng.standard_normal((k, D))).astype(np.float32)
+        for p in range(P):
+            if cw[p] and cn[p] < nn:
+                N[p, cn[p]:] = W[p, rng.integers(0, cw[p], nn - cn[p])]
+            if cn[p] and cw[p] < nw:
+                W[p, cw[p]:] = N[p, rng.integers(0, cn[p], nw - cw[p])]
+        _MEMO[key] = (W, N, cw, cn) if wide_src else (N, W, cn, cw)
+    return _MEMO[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wide_src", [True, False])
+@pytest.mark.parametrize("route", list(ROUTES))
+def test_unequal_sides_on_every_route(oracle, monkeypatch, route, wide_src):
+    """Nmax != Mmax with the two counts on different sides of a tile-padding
+    boundary (513 x 257 and 257 x 513), on each route: a pass that took a
+    count, a stride or a per-cloud array from the wrong side shows only here.
+    nn12, n_corres and the correspondences equal the oracle's bit for bit; the
+    empty pair (no sources, or no targets: index 0) is left to the other checks."""
+    from pointcloudregistration_amd import _lib
+    D, hook, chunks = ROUTES[route]
+    F, G, ns, nt = _unequal_sides(D, wide_src)
+    exp = _expected(oracle, ("unequal_oracle", D, wide_src), F[:3], G[:3], ns, nt)
+    if hook:
+        monkeypatch.setenv(*hook)
+    nn, nc, co = _run(F, G, ns, nt)
+    assert _lib.featnn_image_chunks() == chunks
+    for p in range(3):
+        e12, ec = exp[p]
+        assert np.array_equal(nn[p, :ns[p]], e12), p
+        assert int(nc[p]) == len(ec), p
+        assert np.array_equal(co[p, :len(ec)], ec), p
+    assert not nn[3, :ns[3]].any()
 
 
 @pytest.mark.gpu
