@@ -901,6 +901,61 @@ int pcr_cpd_register(const float *src, const float *tgt, int32_t P, int32_t Mmax
                      double *sigma2, double *q, int32_t *iters, int32_t *status, void *scratch,
                      pcr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * KPConv forward and the neighbour max-pool of NgeNet's encoder: what
+ * KPConv.forward and MaxPoolBlock.forward
+ * (c2p-net/ngenet/models/KPConv/blocks.py:73-128, 182-188) compute from the
+ * input pyramid (pcr_radius_neighbors builds its index tables), for inference,
+ * without the (n,k,C_in) gather, the (n,k,K,3) differences or the (n,K,C_in)
+ * kernel features in global memory.  The f64 restatement is
+ * tests/kpconv_conv_ref.py.
+ *
+ * Inputs.  q_pts (n,3), s_pts (m,3), s_feats (m,c_in), kernel_points (K,3),
+ *   weights (K,c_in,c_out): f32, row-major.  neigh_inds (n,k): int32 or int64,
+ *   index_width = 4 or 8 bytes per index.
+ * Pads.  An index outside [0, m) -- the reference's m, and any negative or larger
+ *   value -- is a pad: it contributes nothing and is never dereferenced.
+ * Influence of a real neighbour j on kernel point e, f32, every operation
+ *   rounded: d2 = (dx dx + dy dy) + dz dz + 1e-8 with d = (s_j - q) - kp_e;
+ *   h = max(0, 1 - sqrt(d2) / kp_extent) for PCR_KP_LINEAR, h = 1 for
+ *   PCR_KP_CONSTANT (aggregation 'sum'; 'cloest' is not built).
+ * Output.  out[i][o] = (sum_e sum_c (sum_j h[i][j][e] f[j][c]) W[e][c][o]) / cnt_i,
+ *   cnt_i = max(1, #{real j : rowsum(f[j][:]) > 0}), rowsum the f32 sum of the
+ *   support row in ascending channel order (a row summing to <= 0 is not
+ *   counted; a query without counted neighbours divides by 1).  A query whose
+ *   neighbours are all pads gives exact zeros.
+ * Numerics.  f32 throughout; both contractions are f32 MFMA fmaf chains
+ *   (v_mfma_f32_16x16x4_f32): over j ascending, then over (e, c) in passes of
+ *   up to 64 channels; where a workgroup holds 32 output channels or fewer the
+ *   (e, c) chain is split over two or four interleaved slices that are added in
+ *   slice order.  The order depends on the sizes only and there are no atomics:
+ *   two calls return the same bytes.  Against the f64
+ *   restatement every output is within
+ *   2^-24 sum_{j,e,c} ((k + K c_in + 16) h + 8) |f| |W| / cnt.
+ * Non-finite inputs: values unspecified; every access stays in range and every
+ *   kernel terminates.
+ * Limits.  1 <= K <= 16, 1 <= k <= 256, c_in and c_out in 1 .. 2048 (no multiple
+ *   of anything), m in 1 .. 2^24, n in 0 .. 2^24, kp_extent > 0 for the linear
+ *   influence.  Anything else, or a null pointer, returns PCR_ERR_ARG with its
+ *   message before any device work; n = 0 returns PCR_OK without a launch.
+ * row_flags: m bytes of device scratch, the call's only one: a pre-pass writes
+ *   rowsum > 0 per support row, the convolution is the second launch.
+ *
+ * pcr_neighbor_max: out[i][ch] = max_j feats[inds[i][j]][ch] over the k columns,
+ *   a pad reading 0; feats (m,c) f32, out (n,c) f32.  Same index rule, widths
+ *   and limits, with c in 1 .. 4096.  Exact on finite data (of equal values the
+ *   first column's is returned).  No (n,k,c) tensor, no scratch.
+ * Both are asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+#define PCR_KP_LINEAR 0
+#define PCR_KP_CONSTANT 1
+int pcr_kpconv_forward(const float *q_pts, const float *s_pts, const float *s_feats, const void *neigh_inds,
+                       int32_t index_width, int32_t n, int32_t m, int32_t k, const float *kernel_points,
+                       const float *weights, int32_t K, int32_t c_in, int32_t c_out, float kp_extent,
+                       int32_t influence, void *row_flags, float *out, pcr_stream_t stream);
+int pcr_neighbor_max(const float *feats, const void *inds, int32_t index_width, int32_t n, int32_t m,
+                     int32_t k, int32_t c, float *out, pcr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,9 @@ SIGNATURES = {
     "pcr_cpd_estep": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _f64, _p, _p, _p, _p, _p, _p],
     "pcr_cpd_register": [_p, _p, _i32, _i32, _i32, _p, _p, _i32, _f64, _i32, _f64, _p, _p, _p, _p, _p, _p, _p,
                          _p, _p],
+    "pcr_kpconv_forward": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _i32, _i32, _i32, _f32, _i32, _p, _p,
+                           _p],
+    "pcr_neighbor_max": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p],
 }
 
 

@@ -225,3 +225,206 @@ def pyramid(points, lengths, normals, architecture, first_subsampling_dl, conv_r
             r_normal *= 2
             layer += 1
     return out
+
+
+# ---------------------------------------------------------------------------
+# The consumers of the pyramid: KPConv.forward and MaxPoolBlock.forward
+# (c2p-net/ngenet/models/KPConv/blocks.py:73-128, 182-188) as one libpcr call
+# each (pcr_kpconv_forward, pcr_neighbor_max; contract in include/pcr_api.h).
+# Inference only: there is no backward.
+# ---------------------------------------------------------------------------
+MAX_KERNEL_POINTS = 16
+MAX_NEIGHBORS = 256
+MAX_CHANNELS = 2048
+MAX_POOL_CHANNELS = 4096
+_INFLUENCE = {"linear": 0, "constant": 1}
+
+
+def _f32(t, name, ncol=None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) "
+                         "library and this module has no CPU path")
+    if not t.dtype.is_floating_point:
+        raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
+    if t.dim() != 2 or (ncol is not None and t.shape[1] != ncol):
+        raise ValueError(f"{name} must be (N, {'C' if ncol is None else ncol}), got {tuple(t.shape)}")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _indices(t, name, rows):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor")
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name} must be torch.int32 or torch.int64, got {t.dtype}")
+    if t.dim() != 2 or t.shape[0] != rows:
+        raise ValueError(f"{name} must be ({rows}, k), got {tuple(t.shape)}")
+    if not 1 <= t.shape[1] <= MAX_NEIGHBORS:
+        raise ValueError(f"{name} has k={t.shape[1]} columns, outside 1..{MAX_NEIGHBORS}")
+    return t.contiguous()
+
+
+def _forward_only(what, *tensors):
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{what} is forward-only (inference): call it under torch.no_grad() or pass "
+                           "detached tensors; it would otherwise silently cut the graph")
+
+
+def kpconv_forward(q_pts, s_pts, s_feats, neigh_inds, kernel_points, weights, KP_extent,
+                   KP_influence="linear"):
+    """KPConv.forward (blocks.py:73-128, aggregation 'sum') as one fused call:
+    q_pts (n,3), s_pts (m,3), s_feats (m,C_in), neigh_inds (n,k) int32/int64 with
+    every index outside [0, m) a pad, kernel_points (K,3), weights
+    (K,C_in,C_out) -> (n,C_out) f32.  Nothing of size n k C_in, n k K or
+    n K C_in is allocated: the output and m bytes of row flags."""
+    if KP_influence not in _INFLUENCE:
+        raise ValueError(f"KP_influence={KP_influence!r}: 'linear' or 'constant'")
+    _forward_only("kpconv_forward", q_pts, s_pts, s_feats, kernel_points, weights)
+    q = _f32(q_pts, "q_pts", 3)
+    s = _f32(s_pts, "s_pts", 3)
+    f = _f32(s_feats, "s_feats")
+    kp = _f32(kernel_points, "kernel_points", 3)
+    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dim() != 3:
+        raise ValueError("weights must be a CUDA tensor of shape (K, C_in, C_out)")
+    w = weights.detach().to(torch.float32).contiguous()
+    n, m = q.shape[0], s.shape[0]
+    K, c_in, c_out = w.shape
+    if m < 1:
+        raise ValueError("s_pts is empty")
+    if f.shape != (m, c_in):
+        raise ValueError(f"s_feats {tuple(f.shape)} must be (m={m}, C_in={c_in})")
+    if kp.shape[0] != K or not 1 <= K <= MAX_KERNEL_POINTS:
+        raise ValueError(f"kernel_points {tuple(kp.shape)} / weights {tuple(w.shape)}: K must agree and lie "
+                         f"in 1..{MAX_KERNEL_POINTS}")
+    if not (1 <= c_in <= MAX_CHANNELS and 1 <= c_out <= MAX_CHANNELS):
+        raise ValueError(f"C_in={c_in}, C_out={c_out} must lie in 1..{MAX_CHANNELS}")
+    idx = _indices(neigh_inds, "neigh_inds", n)
+    if any(t.device != q.device for t in (s, f, kp, w, idx)):
+        raise ValueError("all inputs must live on one device")
+    ext = float(KP_extent)
+    if KP_influence == "linear" and not ext > 0:
+        raise ValueError(f"KP_extent={KP_extent} must be > 0")
+    dev = q.device
+    out = torch.empty((n, c_out), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    flags = torch.empty(m, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("pcr_kpconv_forward", _lib.ptr(q), _lib.ptr(s), _lib.ptr(f), _lib.ptr(idx),
+                  idx.element_size(), n, m, idx.shape[1], _lib.ptr(kp), _lib.ptr(w), K, c_in, c_out, ext,
+                  _INFLUENCE[KP_influence], _lib.ptr(flags), _lib.ptr(out), _lib.stream_handle(dev))
+    return out
+
+
+def neighbor_max(feats, inds):
+    """MaxPoolBlock.forward (blocks.py:182-188): out[i] = max over the columns of
+    feats[inds[i]], a pad (index outside [0, m)) reading 0.  feats (m,C) f32,
+    inds (n,k) int32/int64 -> (n,C) f32, exact."""
+    _forward_only("neighbor_max", feats)
+    f = _f32(feats, "feats")
+    m, c = f.shape
+    if m < 1 or not 1 <= c <= MAX_POOL_CHANNELS:
+        raise ValueError(f"feats {tuple(f.shape)}: needs m >= 1 and C in 1..{MAX_POOL_CHANNELS}")
+    if not isinstance(inds, torch.Tensor) or inds.dim() != 2:
+        raise ValueError("inds must be a (n, k) index tensor")
+    idx = _indices(inds, "inds", inds.shape[0])
+    if idx.device != f.device:
+        raise ValueError("all inputs must live on one device")
+    n = idx.shape[0]
+    out = torch.empty((n, c), dtype=torch.float32, device=f.device)
+    if n == 0:
+        return out
+    with torch.cuda.device(f.device):
+        _lib.call("pcr_neighbor_max", _lib.ptr(f), _lib.ptr(idx), idx.element_size(), n, m, idx.shape[1], c,
+                  _lib.ptr(out), _lib.stream_handle(f.device))
+    return out
+
+
+class KPConv(torch.nn.Module):
+    """The reference's KPConv (blocks.py:44-132) on the fused op, with its
+    attribute names and state-dict keys (`weights`, `kernel_points`).  Built from
+    given kernel points (K,3); it reads no kernel-point files.  `weights` may be
+    an existing Parameter to share (fuse()), else it is initialised as there."""
+
+    def __init__(self, in_channels, out_channels, radius, kernel_points, KP_extent, KP_influence="linear",
+                 aggregation_mode="sum", weights=None):
+        super().__init__()
+        if aggregation_mode != "sum":
+            raise NotImplementedError(f"aggregation_mode={aggregation_mode!r}: only 'sum' is built")
+        if KP_influence not in _INFLUENCE:
+            raise NotImplementedError(f"KP_influence={KP_influence!r}: 'linear' or 'constant'")
+        if isinstance(kernel_points, torch.nn.Parameter):
+            kp = kernel_points
+        else:
+            kp = torch.nn.Parameter(torch.as_tensor(kernel_points, dtype=torch.float32).clone(),
+                                    requires_grad=False)
+        if kp.dim() != 2 or kp.shape[1] != 3:
+            raise ValueError(f"kernel_points must be (K, 3), got {tuple(kp.shape)}")
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        self.radius = radius
+        self.K = kp.shape[0]
+        self.KP_extent = KP_extent
+        self.KP_influence = KP_influence
+        self.aggregation_mode = aggregation_mode
+        if weights is None:
+            weights = torch.nn.Parameter(torch.zeros((self.K, self.in_channels, self.out_channels),
+                                                     dtype=torch.float32))
+            torch.nn.init.kaiming_uniform_(weights, a=5 ** 0.5)
+        if tuple(weights.shape) != (self.K, self.in_channels, self.out_channels):
+            raise ValueError(f"weights {tuple(weights.shape)} must be (K, in_channels, out_channels) = "
+                             f"{(self.K, self.in_channels, self.out_channels)}")
+        self.weights = weights
+        self.kernel_points = kp
+
+    def forward(self, q_pts, s_pts, s_feats, neigh_inds):
+        return kpconv_forward(q_pts, s_pts, s_feats, neigh_inds, self.kernel_points, self.weights,
+                              self.KP_extent, self.KP_influence)
+
+    def __repr__(self):
+        return "KPConv(radius: {:.2f}, nkernels: {:d}, in_feat: {:d}, out_feat: {:d})".format(
+            self.radius, self.K, self.in_channels, self.out_channels)
+
+
+class MaxPool(torch.nn.Module):
+    """MaxPoolBlock (blocks.py:177-188) on neighbor_max."""
+
+    def __init__(self, layer_ind):
+        super().__init__()
+        self.layer_ind = layer_ind
+
+    def forward(self, feats, batch):
+        return neighbor_max(feats, batch["pools"][self.layer_ind])
+
+
+def _conv_shaped(mod):
+    w, kp = getattr(mod, "weights", None), getattr(mod, "kernel_points", None)
+    return (isinstance(w, torch.Tensor) and w.dim() == 3 and isinstance(kp, torch.Tensor) and kp.dim() == 2
+            and kp.shape[1] == 3 and kp.shape[0] == w.shape[0] and hasattr(mod, "KP_extent")
+            and getattr(mod, "aggregation_mode", None) == "sum" and not isinstance(mod, KPConv))
+
+
+def fuse(model):
+    """Swap the torch composites of a loaded network for the fused ops, in place:
+    every submodule with `weights` (K,C_in,C_out), `kernel_points` (K,3),
+    `KP_extent` and aggregation_mode 'sum' becomes a KPConv sharing the same
+    parameters, every MaxPoolBlock (by class name, with `layer_ind`) a MaxPool.
+    Returns (convolutions swapped, pools swapped)."""
+    n_conv = n_pool = 0
+    for parent in list(model.modules()):
+        for name, child in list(parent.named_children()):
+            if _conv_shaped(child):
+                new = KPConv(child.weights.shape[1], child.weights.shape[2], getattr(child, "radius", 0.0),
+                             child.kernel_points, child.KP_extent, getattr(child, "KP_influence", "linear"),
+                             "sum", weights=child.weights)
+                n_conv += 1
+            elif type(child).__name__ == "MaxPoolBlock" and hasattr(child, "layer_ind"):
+                new = MaxPool(child.layer_ind)
+                n_pool += 1
+            else:
+                continue
+            new.train(child.training)
+            setattr(parent, name, new)
+    return n_conv, n_pool
