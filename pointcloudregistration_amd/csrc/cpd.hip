@@ -31,6 +31,7 @@
 // sweep 3 + 5 + 2, 0.75 (3 add per 4): 10.75 plain + 1 exp + 0.5 f64.
 #include "pcr_internal.h"
 #include "geom.h"
+#include "wave.h"
 #include <float.h>
 
 namespace pcr {
@@ -580,7 +581,6 @@ __global__ void cpd_export_kernel(OutArgs a, int P) {
     a.iters[p] = (int)st[kStIters];
 }
 
-inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // slices of the staged axis (len points) for a sweep whose lanes cover `lanes`

@@ -481,10 +481,6 @@ static int feature_corres_v5(const float *F, const float *G, int P, int Nmax, in
     return PCR_OK;
 }
 
-int corres_impl(const int32_t *nn12, const int32_t *nn21, const int32_t *n_src,
-                const int32_t *n_tgt, int P, int Nmax, int Mmax, int mutual, int ransac_n,
-                int32_t *corres, int32_t *n_corres, hipStream_t s);
-
 int feature_corres_impl(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
                         const int32_t *n_src, const int32_t *n_tgt, int mutual, int ransac_n,
                         int32_t *nn12, int32_t *corres, int32_t *n_corres, hipStream_t s) {

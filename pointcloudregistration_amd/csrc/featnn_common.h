@@ -2,15 +2,12 @@
 // featnn_f32.hip: augmented f32 operands, 64 < D <= 128).
 #pragma once
 #include "pcr_internal.h"
+#include "wave.h"
 
 namespace pcr {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int count_of(const int32_t *n, int p, int Nmax) {
-    return n ? min(max(n[p], 0), Nmax) : Nmax;
-}
 
 // merge two top-2 states; lowest index wins equal minima.  Branch-free: the
 // screen's values are finite or +inf (never NaN), so plain selects are exact.
@@ -23,8 +20,6 @@ __device__ __forceinline__ void top2_merge(float &b1, int &i1, float &b2, float 
     i1 = take ? oi : i1;
     b2 = n2;
 }
-
-inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
 

@@ -27,6 +27,7 @@
 // All are HBM/L2-latency bound at the reference's sizes (tens of neighbours).
 #include "pcr_internal.h"
 #include "grid.h"
+#include "wave.h"
 
 #include <climits>
 
@@ -112,10 +113,6 @@ struct SearchArgs {
     double *d2;                // (P, N, K)
     int32_t *cnt;              // (P, N)
 };
-
-__device__ __forceinline__ int count_of(const int32_t *n, int p, int N) {
-    return n ? min(max(n[p], 0), N) : N;
-}
 
 // ascending bitonic sort of (key, idx) over m = pow2 entries, one wave
 __device__ void wave_sort(unsigned long long *key, int *id, int m) {

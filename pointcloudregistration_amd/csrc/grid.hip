@@ -20,10 +20,6 @@ struct BuildArgs {
     float4 *pts;   // P*Mmax: x, y, z, index bits (one 16-B store per point)
 };
 
-__device__ __forceinline__ int count_of(const int32_t *n, int p, int Mmax) {
-    return n ? min(max(n[p], 0), Mmax) : Mmax;
-}
-
 __global__ void grid_count(BuildArgs a) {
     const int p = blockIdx.y;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;

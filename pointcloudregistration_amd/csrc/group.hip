@@ -30,21 +30,16 @@
 // -ffp-contract=off); neighbour iff !(d2 > r2).  Non-finite coordinates give
 // unspecified results.
 #include "pcr_internal.h"
+#include "wave.h"
 #include <math.h>
 
 namespace {
 
+using pcr::cdiv, pcr::d2_direct, pcr::u64;
+
 constexpr int kFpsThreads = 1024;
 constexpr int kFpsWaves = kFpsThreads / 64;
 constexpr int kFpsRegPoints = 8 * kFpsThreads;  // 8192: the register path's capacity
-
-__device__ __forceinline__ float d2_direct(float ax, float ay, float az, float bx, float by,
-                                           float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-typedef unsigned long long u64;
 
 __device__ __forceinline__ u64 fps_key(float d, int j) {
     return ((u64)__float_as_uint(d) << 32) | (unsigned)~j;
@@ -336,7 +331,6 @@ __global__ __launch_bounds__(kPfThreads) void ppf_cl_kernel(PpfArgs a) {
     }
 }
 
-inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 int launch_ball_query(const float *xyz, const float *query, int b, int n, int q, float r2, int k,
                       int32_t *idx, int32_t *count, hipStream_t s) {

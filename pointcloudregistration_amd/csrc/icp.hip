@@ -28,6 +28,7 @@
 #include "coop.h"
 #include "geom.h"
 #include "grid.h"
+#include "wave.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -122,10 +123,6 @@ __device__ __forceinline__ void put_step(int4 *q, int z, bool wt) {
 
 // a listed pair's state: T (16), C (9), ms (3), mt (3), fit, rmse, count, it
 constexpr int kSave = 36;
-
-__device__ __forceinline__ int cnt_of(const int32_t *n, int p, int mx) {
-    return n ? min(max(n[p], 0), mx) : mx;
-}
 
 struct IShared {  // LDS header; the grid copy (if any) follows
     double ws[kWaves][kQ];
@@ -260,8 +257,8 @@ __global__ __launch_bounds__(kThreads) void icp_kernel(IArgs a) {
         g = blockIdx.x - p * G;
     }
     const bool resume = a.phase == 2;
-    const int n = cnt_of(a.n_src, p, a.Nmax);
-    const int m = cnt_of(a.n_tgt, p, a.Mmax);
+    const int n = count_of(a.n_src, p, a.Nmax);
+    const int m = count_of(a.n_tgt, p, a.Mmax);
     const int tid = threadIdx.x, lane = tid & 63;
     const float *S = a.src + (size_t)p * a.Nmax * 3;
     const int32_t *ord = a.order ? a.order + (size_t)p * a.Nmax : nullptr;

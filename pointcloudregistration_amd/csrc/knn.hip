@@ -34,10 +34,11 @@
 // -ffp-contract=off); f_j - f_i is one f32 subtraction.  Non-finite
 // coordinates give unspecified results.
 #include "pcr_internal.h"
+#include "wave.h"
 
 namespace {
 
-typedef unsigned long long u64;
+using pcr::cdiv64, pcr::d2_direct, pcr::u64;
 
 constexpr int kKnThreads = 256;
 constexpr int kKnWaves = kKnThreads / 64;
@@ -46,12 +47,6 @@ constexpr int kKnPerBlock = kKnWaves * kKnPerWave;   // 16
 constexpr int kKnChunk = 2048;                       // points per LDS stage (24 KiB)
 constexpr int kKnMaxK = 63;                          // kk + 1 keys fit one wave
 constexpr u64 kKnNoKey = ~(u64)0;                    // above every real key
-
-__device__ __forceinline__ float d2_direct(float ax, float ay, float az, float bx, float by,
-                                           float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
 
 __device__ __forceinline__ u64 knn_key(float d, int j) {
     return ((u64)__float_as_uint(d) << 32) | (unsigned)j;
@@ -255,7 +250,6 @@ __global__ __launch_bounds__(kEfThreads) void edge_cf_kernel(EdgeArgs a) {
     }
 }
 
-inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
 
 // the limit the grouping entries share: the kernels form point offsets 3 j in int
 constexpr long long kMaxPoints = (1LL << 31) / 3 - 1;
@@ -274,7 +268,7 @@ extern "C" int pcr_knn_graph(const float *xyz, int32_t b, int32_t n, int32_t k, 
     if (b == 0 || kk == 0) return PCR_OK;
     PCR_REQUIRE(xyz && idx, PCR_ERR_ARG, "knn_graph: null pointer");
     KnnArgs a{xyz, idx, d2, n, kk};
-    hipLaunchKernelGGL(knn_graph_kernel, dim3((unsigned)cdivll(n, kKnPerBlock), b), dim3(kKnThreads), 0,
+    hipLaunchKernelGGL(knn_graph_kernel, dim3((unsigned)cdiv64(n, kKnPerBlock), b), dim3(kKnThreads), 0,
                        pcr::as_stream(stream), a);
     PCR_LAUNCH_CHECK();
     return PCR_OK;
@@ -288,17 +282,17 @@ extern "C" int pcr_edge_features(const float *feats, const int32_t *idx, int32_t
     PCR_REQUIRE(n >= 1 && c >= 1, PCR_ERR_ARG, "edge_features: n=%d, c=%d (both must be >= 1)", n, c);
     PCR_REQUIRE(kk >= 0 && kk <= kKnMaxK, PCR_ERR_ARG, "edge_features: kk=%d outside 0..%d", kk, kKnMaxK);
     PCR_REQUIRE(n <= kMaxPoints, PCR_ERR_ARG, "edge_features: n=%d too large", n);
-    PCR_REQUIRE(b <= 65535 && cdivll(c, kEfTile) <= 65535, PCR_ERR_ARG,
+    PCR_REQUIRE(b <= 65535 && cdiv64(c, kEfTile) <= 65535, PCR_ERR_ARG,
                 "edge_features: b=%d or c=%d too large", b, c);
     if (b == 0 || kk == 0) return PCR_OK;
     PCR_REQUIRE(feats && idx && out, PCR_ERR_ARG, "edge_features: null pointer");
     hipStream_t s = pcr::as_stream(stream);
     EdgeArgs a{feats, idx, out, n, c, kk};
     if (channels_first) {
-        const dim3 grid((unsigned)cdivll((long long)n * kk, kEfTile), (unsigned)cdivll(c, kEfTile), b);
+        const dim3 grid((unsigned)cdiv64((long long)n * kk, kEfTile), (unsigned)cdiv64(c, kEfTile), b);
         hipLaunchKernelGGL(edge_cf_kernel, grid, dim3(kEfThreads), 0, s, a);
     } else {
-        const dim3 grid((unsigned)cdivll(n, kEfWaves), b);
+        const dim3 grid((unsigned)cdiv64(n, kEfWaves), b);
         const bool wide = c % 4 == 0 && (((uintptr_t)feats | (uintptr_t)out) & 15) == 0;
         if (wide) hipLaunchKernelGGL(edge_cl_kernel<4>, grid, dim3(kEfThreads), 0, s, a);
         else hipLaunchKernelGGL(edge_cl_kernel<1>, grid, dim3(kEfThreads), 0, s, a);

@@ -33,6 +33,7 @@
 // the reference's tree (kdreplay.cpp).  Every other row is decided by distance
 // alone, so the (distance, index) sort gives the reference's order.
 #include "pcr_internal.h"
+#include "voxel_runs.h"
 
 #include <cstring>
 
@@ -44,14 +45,7 @@
 #include <vector>
 
 namespace pcr {
-
-// kdreplay.cpp
-void kd_replay_rows(const float *q, const float *s, const int *soff, const std::vector<int> &rows,
-                    const std::vector<int> &qbatch, float r2, std::vector<std::vector<int>> &res);
-
 namespace {
-
-typedef unsigned long long u64;
 
 // ---------------------------------------------------------------------------
 // grid subsampling
@@ -78,15 +72,6 @@ struct GsArgs {
     int *bat;         // [n] batch of point
 };
 
-__device__ __forceinline__ int batch_of(const int *off, int nb, int i) {
-    int lo = 0, hi = nb - 1;  // largest b with off[b] <= i
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // one block per batch: min/max corners (cloud.cpp min_point/max_point :27-68),
 // origin corner and grid extents (grid_subsampling.cpp :23-31)
 __global__ __launch_bounds__(256) void gs_bbox(GsArgs a) {
@@ -102,40 +87,25 @@ __global__ __launch_bounds__(256) void gs_bbox(GsArgs a) {
             lo[c] = fminf(lo[c], v);
             hi[c] = fmaxf(hi[c], v);
         }
-    __shared__ float sl[3][4], sh[3][4];
-    __shared__ int sb[4];
-    for (int c = 0; c < 3; ++c)
-        for (int o = 32; o; o >>= 1) {
-            lo[c] = fminf(lo[c], __shfl_xor(lo[c], o, 64));
-            hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], o, 64));
-        }
-    for (int o = 32; o; o >>= 1) bad |= __shfl_xor(bad, o, 64);
-    if ((t & 63) == 0) {
-        for (int c = 0; c < 3; ++c) { sl[c][t >> 6] = lo[c]; sh[c][t >> 6] = hi[c]; }
-        sb[t >> 6] = bad;
-    }
-    __syncthreads();
+    bad = block_bbox<float, 4>(lo, hi, bad);
     if (t != 0) return;
-    if (sb[0] | sb[1] | sb[2] | sb[3]) atomicOr(a.bad, 1);
+    if (bad) atomicOr(a.bad, 1);
     if (i1 <= i0) return;
     const float inv = __fdiv_rn(1.0f, a.dl);  // (1/sampleDl): int / float
-    float org[3], mx[3];
+    float org[3];
     for (int c = 0; c < 3; ++c) {
-        float l = sl[c][0], h = sh[c][0];
-        for (int w = 1; w < 4; ++w) { l = fminf(l, sl[c][w]); h = fmaxf(h, sh[c][w]); }
-        org[c] = __fmul_rn(floorf(__fmul_rn(l, inv)), a.dl);
-        mx[c] = h;
+        org[c] = __fmul_rn(floorf(__fmul_rn(lo[c], inv)), a.dl);
         a.origin[3 * b + c] = org[c];
     }
-    a.nxy[2 * b] = f2size(floorf(__fdiv_rn(__fsub_rn(mx[0], org[0]), a.dl))) + 1ull;
-    a.nxy[2 * b + 1] = f2size(floorf(__fdiv_rn(__fsub_rn(mx[1], org[1]), a.dl))) + 1ull;
+    a.nxy[2 * b] = f2size(floorf(__fdiv_rn(__fsub_rn(hi[0], org[0]), a.dl))) + 1ull;
+    a.nxy[2 * b + 1] = f2size(floorf(__fdiv_rn(__fsub_rn(hi[1], org[1]), a.dl))) + 1ull;
 }
 
 // grid_subsampling.cpp :50-54
 __global__ void gs_key(GsArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.off[a.nb]) return;
-    const int b = batch_of(a.off, a.nb, i);
+    const int b = segment_of(a.off, a.nb, i);
     const float *p = a.pts + 3 * (size_t)i;
     const float *o = a.origin + 3 * b;
     const u64 ix = f2size(floorf(__fdiv_rn(__fsub_rn(p[0], o[0]), a.dl)));
@@ -146,46 +116,6 @@ __global__ void gs_key(GsArgs a) {
     a.key[i] = k;
     a.bat[i] = b;
     atomicMax(a.maxkey, k);
-}
-
-__global__ void gs_compose(const u64 *key, const int *bat, int n, int kbits, u64 *ck, int *iota) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    ck[i] = kbits < 64 ? (((u64)bat[i] << kbits) | key[i]) : key[i];
-    iota[i] = i;
-}
-
-__global__ void gs_batch_key(const int *bat, const int *v, int n, u64 *ck) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) ck[i] = (u64)bat[v[i]];
-}
-
-// run heads of the (batch, key)-sorted points
-__global__ void gs_heads(const u64 *key, const int *bat, const int *v, int n, unsigned char *head) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int a = v[i];
-    head[i] = (i == 0) || bat[a] != bat[v[i - 1]] || key[a] != key[v[i - 1]];
-}
-
-// mark[first point of voxel] = voxel id (the sort is stable: a run's first
-// entry is its lowest input index)
-__global__ void gs_mark(const int *start, const int *v, int V, int *mark) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < V) mark[v[start[r]]] = r;
-}
-
-struct NonNeg {
-    __device__ bool operator()(int x) const { return x >= 0; }
-};
-
-__global__ void gs_okey(const int *list, const int *start, const int *v, const u64 *key,
-                        const int *bat, int V, u64 *okey, int *obat) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= V) return;
-    const int first = v[start[list[r]]];
-    okey[r] = key[first];
-    obat[r] = bat[first];
 }
 
 // barycentres and mean features, written to their output slot: sums in input
@@ -218,8 +148,6 @@ __global__ void gs_emit(GsArgs a, const int *outr, int total, const int *list, c
         }
     }
 }
-
-inline unsigned nbits(u64 x) { return x ? 64u - (unsigned)__builtin_clzll(x) : 0u; }
 
 // ---------------------------------------------------------------------------
 // radius neighbours
@@ -275,7 +203,7 @@ __global__ void rn_grid(RnArgs a) {
         if (!SCATTER) atomicOr(a.bad, 1);
         return;
     }
-    const unsigned h = rhash(batch_of(a.soff, a.nb, i), x, y, z, a.S);
+    const unsigned h = rhash(segment_of(a.soff, a.nb, i), x, y, z, a.S);
     if (!SCATTER) {
         atomicAdd(a.hcnt + h, 1);
     } else {
@@ -296,7 +224,7 @@ __global__ __launch_bounds__(256) void rn_query(RnArgs a) {
     if (FILL && qi0 >= a.nq) return;
     const bool live = qi0 < a.nq;
     const int qi = live ? qi0 : a.nq - 1;  // idle lanes join the count reduction with 0
-    const int b = batch_of(a.qoff, a.nb, qi);
+    const int b = segment_of(a.qoff, a.nb, qi);
     const int s0 = a.soff[b], s1 = a.soff[b + 1];
     const float *qp = a.q + 3 * (size_t)qi;
     const float qx = qp[0], qy = qp[1], qz = qp[2];
@@ -342,8 +270,7 @@ __global__ __launch_bounds__(256) void rn_query(RnArgs a) {
         if (live && edge) a.blist[atomicAdd(a.bcnt, 1)] = qi;
         if (live) a.counts[qi] = cnt;
         atomicMax(a.maxcnt, cnt);
-        u64 t = (u64)cnt;
-        for (int o = 32; o; o >>= 1) t += __shfl_xor(t, o, 64);
+        const u64 t = wave_sum((u64)cnt);
         if ((threadIdx.x & 63) == 0) atomicAdd(a.total, t);
     }
 }
@@ -560,15 +487,14 @@ extern "C" int pcr_grid_subsample(const float *points, int32_t n, const int32_t 
     if (N == 0) return PCR_OK;
     hipStream_t st = as_stream(stream);
     GsArgs a;
-    u64 *ck, *ck2, *okey;
-    int *iota, *v, *v2, *start, *mark, *list, *obat, *outr, *dcnt;
-    unsigned char *head;
+    VoxelRuns r;
+    int *outr;
     WsLayout l(256);
     l.take(a.off, nb + 1); l.take(a.origin, 3 * nb); l.take(a.nxy, 2 * nb); l.take(a.maxkey, 2);
     l.take(a.key, N); l.take(a.bat, N);
-    l.take(ck, N); l.take(ck2, N); l.take(iota, N); l.take(v, N); l.take(v2, N);
-    l.take(head, N); l.take(start, N + 1); l.take(mark, N); l.take(list, N);
-    l.take(okey, N); l.take(obat, N); l.take(outr, N); l.take(dcnt, 2);
+    l.take(r.ck, N); l.take(r.ck2, N); l.take(r.v, N); l.take(r.v2, N);
+    l.take(r.head, N); l.take(r.start, N + 1); l.take(r.mark, N); l.take(r.list, N);
+    l.take(r.okey, N); l.take(r.ocloud, N); l.take(outr, N); l.take(r.dcnt, 2);
     PCR_REQUIRE(workspace_bind(kWsSubsample, l), PCR_ERR_NOMEM, "grid_subsample: %s", pcr_last_error());
     a.pts = points; a.feat = fdim > 0 ? features : nullptr; a.n = N; a.fdim = fdim; a.nb = nb;
     a.dl = dl;
@@ -588,51 +514,13 @@ extern "C" int pcr_grid_subsample(const float *points, int32_t n, const int32_t 
                 "grid_subsample: non-finite point coordinates (the reference's voxel index is undefined there)");
     const unsigned kbits = nbits(hk[0]) ? nbits(hk[0]) : 1u, bbits = nbits((u64)(nb - 1));
 
-    // stable radix sort by (batch, key): input order kept inside a voxel
-    size_t tb = 0, t1 = 0;
-    PCR_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, t1, ck, ck2, iota, v, N, 0, 64, st));
-    tb = t1;
-    PCR_HIP_CHECK(rocprim::select(nullptr, t1, rocprim::counting_iterator<int>(0), head, start, dcnt, (size_t)N, st));
-    tb = tb > t1 ? tb : t1;
-    PCR_HIP_CHECK(rocprim::select(nullptr, t1, mark, list, dcnt + 1, (size_t)N, NonNeg(), st));
-    tb = tb > t1 ? tb : t1;
-    void *tmp = workspace(kWsSubsampleTmp, tb);
-    PCR_REQUIRE(tmp, PCR_ERR_NOMEM, "grid_subsample: %s", pcr_last_error());
-    if (kbits + bbits <= 64) {
-        hipLaunchKernelGGL(gs_compose, gN, blk, 0, st, a.key, a.bat, N, (int)kbits, ck, iota);
-        PCR_LAUNCH_CHECK();
-        t1 = tb;
-        PCR_HIP_CHECK(rocprim::radix_sort_pairs(tmp, t1, ck, ck2, iota, v, N, 0, kbits + bbits, st));
-    } else {  // keys wider than the composite: LSD in two stable passes
-        hipLaunchKernelGGL(gs_compose, gN, blk, 0, st, a.key, a.bat, N, 64, ck, iota);
-        PCR_LAUNCH_CHECK();
-        t1 = tb;
-        PCR_HIP_CHECK(rocprim::radix_sort_pairs(tmp, t1, ck, ck2, iota, v2, N, 0, kbits, st));
-        hipLaunchKernelGGL(gs_batch_key, gN, blk, 0, st, a.bat, v2, N, ck);
-        PCR_LAUNCH_CHECK();
-        t1 = tb;
-        PCR_HIP_CHECK(rocprim::radix_sort_pairs(tmp, t1, ck, ck2, v2, v, N, 0, bbits ? bbits : 1u, st));
-    }
-    hipLaunchKernelGGL(gs_heads, gN, blk, 0, st, a.key, a.bat, v, N, head);
-    PCR_LAUNCH_CHECK();
-    t1 = tb;
-    PCR_HIP_CHECK(rocprim::select(tmp, t1, rocprim::counting_iterator<int>(0), head, start, dcnt, (size_t)N, st));
     int V = 0;
-    PCR_HIP_CHECK(hipMemcpyAsync(&V, dcnt, sizeof(int), hipMemcpyDeviceToHost, st));
-    PCR_HIP_CHECK(hipStreamSynchronize(st));
-    PCR_HIP_CHECK(hipMemcpyAsync(start + V, &N, sizeof(int), hipMemcpyHostToDevice, st));
-    PCR_HIP_CHECK(hipMemsetAsync(mark, 0xFF, sizeof(int) * N, st));
-    const dim3 gV((V + 255) / 256);
-    hipLaunchKernelGGL(gs_mark, gV, blk, 0, st, start, v, V, mark);
-    PCR_LAUNCH_CHECK();
-    t1 = tb;
-    PCR_HIP_CHECK(rocprim::select(tmp, t1, mark, list, dcnt + 1, (size_t)N, NonNeg(), st));
-    hipLaunchKernelGGL(gs_okey, gV, blk, 0, st, list, start, v, a.key, a.bat, V, okey, obat);
-    PCR_LAUNCH_CHECK();
+    const int rc = voxel_runs(a.key, kbits, a.bat, bbits, N, r, kWsSubsampleTmp, "grid_subsample", st, &V);
+    if (rc != PCR_OK) return rc;
     std::vector<u64> hkey(V);
     std::vector<int> hbat(V), hout;
-    PCR_HIP_CHECK(hipMemcpyAsync(hkey.data(), okey, sizeof(u64) * V, hipMemcpyDeviceToHost, st));
-    PCR_HIP_CHECK(hipMemcpyAsync(hbat.data(), obat, sizeof(int) * V, hipMemcpyDeviceToHost, st));
+    PCR_HIP_CHECK(hipMemcpyAsync(hkey.data(), r.okey, sizeof(u64) * V, hipMemcpyDeviceToHost, st));
+    PCR_HIP_CHECK(hipMemcpyAsync(hbat.data(), r.ocloud, sizeof(int) * V, hipMemcpyDeviceToHost, st));
     PCR_HIP_CHECK(hipStreamSynchronize(st));
     // per cloud: the map's iteration order, truncated to max_p (:180-204)
     const int cap = max_p < 1 ? n : max_p;  // :134-135 (N = all points of the call)
@@ -649,7 +537,7 @@ extern "C" int pcr_grid_subsample(const float *points, int32_t n, const int32_t 
     }
     const int total = (int)hout.size();
     PCR_HIP_CHECK(hipMemcpyAsync(outr, hout.data(), sizeof(int) * total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(gs_emit, dim3((total + 255) / 256), blk, 0, st, a, outr, total, list, start, v,
+    hipLaunchKernelGGL(gs_emit, dim3((total + 255) / 256), blk, 0, st, a, outr, total, r.list, r.start, r.v,
                        out_points, fdim > 0 ? out_features : nullptr);
     PCR_LAUNCH_CHECK();
     PCR_HIP_CHECK(hipStreamSynchronize(st));  // hout is a host temporary

@@ -21,15 +21,12 @@
 // is the traffic.
 #include "pcr_internal.h"
 #include "geom.h"
+#include "wave.h"
 
 namespace pcr {
 namespace {
 
 constexpr int kT = 256;
-
-__device__ __forceinline__ int cnt_of(const int32_t *n, int p, int nmax) {
-    return n ? min(max(n[p], 0), nmax) : nmax;
-}
 
 __device__ __forceinline__ double lrf_thr(double kernel) { return (double)(float)(kernel * kernel); }
 
@@ -50,8 +47,8 @@ __global__ __launch_bounds__(kT) void lrf_count_kernel(const double *pts, int Nm
                                                        int Qmax, const int32_t *n_q, double kernel,
                                                        int32_t *counts) {
     const int p = blockIdx.y, qi = blockIdx.x;
-    if (qi >= cnt_of(n_q, p, Qmax)) return;
-    const int n = cnt_of(n_pts, p, Nmax);
+    if (qi >= count_of(n_q, p, Qmax)) return;
+    const int n = count_of(n_pts, p, Nmax);
     const double *P = pts + (size_t)p * Nmax * 3;
     const double *q = qs + ((size_t)p * Qmax + qi) * 3;
     const double qx = q[0], qy = q[1], qz = q[2], thr = lrf_thr(kernel);
@@ -131,8 +128,8 @@ __global__ __launch_bounds__(kT) void lrf_frame_kernel(LrfArgs a) {
     __shared__ double frame[12];  // xp yp zp pt
     __shared__ int s_k;
     const int p = blockIdx.y, qi = blockIdx.x, t = threadIdx.x;
-    if (qi >= cnt_of(a.n_q, p, a.Qmax)) return;
-    const int n = cnt_of(a.n_pts, p, a.Nmax);
+    if (qi >= count_of(a.n_q, p, a.Qmax)) return;
+    const int n = count_of(a.n_pts, p, a.Nmax);
     const double *P = a.pts + (size_t)p * a.Nmax * 3;
     const double *q = a.qs + ((size_t)p * a.Qmax + qi) * 3;
     const double qx = q[0], qy = q[1], qz = q[2], thr = lrf_thr(a.kernel);

@@ -27,6 +27,8 @@
 
 namespace {
 
+using pcr::cdiv;
+
 constexpr int kThreads = 256;
 constexpr int kTileBig = 512;    // candidates per LDS stage (6 KiB)
 constexpr int kTileSmall = 128;  // small problems: more, shorter slices
@@ -339,7 +341,6 @@ __global__ void bw_chain(BwdArgs a) {
     }
 }
 
-inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
 

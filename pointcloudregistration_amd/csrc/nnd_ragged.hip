@@ -20,8 +20,11 @@
 // (pcr_nnd_forward serves homogeneous f32 batches); sized for the validation
 // and loss calls of the reference's scripts.
 #include "pcr_internal.h"
+#include "wave.h"
 
 namespace {
+
+using pcr::cdiv;
 
 constexpr int kRThreads = 256;
 constexpr int kRQ = 2;          // queries per lane
@@ -142,7 +145,6 @@ __global__ __launch_bounds__(256) void nnd_ragged_merge(RaggedArgs<Scalar> a) {
     (dir ? a.idx2 : a.idx1)[(size_t)bat * cap_q + qi] = j;
 }
 
-inline int rcdiv(long long x, long long y) { return (int)((x + y - 1) / y); }
 
 template <typename Scalar>
 int nnd_ragged(const Scalar *xyz1, const Scalar *xyz2, int32_t b, int32_t n, int32_t m,
@@ -156,7 +158,7 @@ int nnd_ragged(const Scalar *xyz1, const Scalar *xyz2, int32_t b, int32_t n, int
     PCR_REQUIRE(2LL * b <= 65535, PCR_ERR_ARG, "nnd_forward_ragged: b=%d too large (max 32767)", b);
     hipStream_t s = pcr::as_stream(stream);
     const int nmax = n > m ? n : m;
-    const int qtiles = rcdiv(nmax, kRThreads * kRQ);
+    const int qtiles = cdiv(nmax, kRThreads * kRQ);
     // split the candidate axis until the launch has >= ~4 blocks per CU
     int slices = 1;
     while ((long long)qtiles * 2 * b * slices < 4LL * pcr::kCUs && (long long)kRTile * slices * 2 <= nmax)
@@ -165,8 +167,8 @@ int nnd_ragged(const Scalar *xyz1, const Scalar *xyz2, int32_t b, int32_t n, int
     a.xyz1 = xyz1; a.xyz2 = xyz2; a.n1 = n1; a.n2 = n2;
     a.dist1 = dist1; a.dist2 = dist2; a.idx1 = idx1; a.idx2 = idx2;
     a.b = b; a.n = n; a.m = m; a.nmax = nmax;
-    a.slice_len = rcdiv(rcdiv(nmax, slices), kRTile) * kRTile;
-    a.slices = rcdiv(nmax, a.slice_len);
+    a.slice_len = cdiv(cdiv(nmax, slices), kRTile) * kRTile;
+    a.slices = cdiv(nmax, a.slice_len);
     const size_t cells = (size_t)a.slices * 2 * b * nmax;
     pcr::WsLayout l;
     l.take(a.pd, cells);
@@ -176,7 +178,7 @@ int nnd_ragged(const Scalar *xyz1, const Scalar *xyz2, int32_t b, int32_t n, int
     hipLaunchKernelGGL(nnd_ragged_kernel<Scalar>, dim3(qtiles, a.slices, 2 * b), dim3(kRThreads), 0,
                        s, a);
     PCR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(nnd_ragged_merge<Scalar>, dim3(rcdiv(nmax, 256), 1, 2 * b), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(nnd_ragged_merge<Scalar>, dim3(cdiv(nmax, 256), 1, 2 * b), dim3(256), 0, s, a);
     PCR_LAUNCH_CHECK();
     return PCR_OK;
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <vector>
 #include "../../include/pcr_api.h"
 #include "workspace.h"
 
@@ -70,6 +71,34 @@ void prof_end(hipStream_t s, int id);
 // left after the break do no work.  Null: ungated (every other caller).
 const double *current_gate();
 __device__ __forceinline__ bool gated_off(const double *g) { return g != nullptr && *g == 0.0; }
+
+// Functions one unit defines and another calls, each declared here only.
+// featnn.hip (NN matching, correspondences from NN lists, both at once),
+// ransac.hip, icp.hip (null grid / order / perm: built inside), procrustes.hip,
+// kdreplay.cpp (the reference's neighbour lists of `rows`, for kpconv.hip)
+struct GridBatch;  // grid.h
+int feature_match_impl(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
+                       const int32_t *n_src, const int32_t *n_tgt, int32_t *nn12, int32_t *nn21,
+                       hipStream_t s);
+int feature_corres_impl(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
+                        const int32_t *n_src, const int32_t *n_tgt, int mutual, int ransac_n,
+                        int32_t *nn12, int32_t *corres, int32_t *n_corres, hipStream_t s);
+int corres_impl(const int32_t *nn12, const int32_t *nn21, const int32_t *n_src,
+                const int32_t *n_tgt, int P, int Nmax, int Mmax, int mutual, int ransac_n,
+                int32_t *corres, int32_t *n_corres, hipStream_t s);
+int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
+                const int32_t *n_src, const int32_t *n_tgt, const int32_t *corres,
+                const int32_t *n_corres, int Kmax, const uint32_t *pair_ids,
+                const pcr_ransac_params *prm, double *T_out, double *fit_out, int32_t *stats,
+                int32_t *corr_tgt, uint32_t *mask, hipStream_t s, const int32_t **order_out,
+                const GridBatch *grid_in, const int32_t *order_in, const float *perm_in);
+int icp_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax, const int32_t *n_src,
+             const int32_t *n_tgt, const double *init, const pcr_icp_params *prm, double *T_out,
+             double *fit_out, int32_t *stats, int32_t *corr_tgt, hipStream_t s, const int32_t *order_in,
+             const GridBatch *grid_in, const float *perm_in);
+int pipeline_records(const pcr_pipeline_io *io, hipStream_t s);
+void kd_replay_rows(const float *q, const float *s, const int *soff, const std::vector<int> &rows,
+                    const std::vector<int> &qbatch, float r2, std::vector<std::vector<int>> &res);
 
 constexpr int kWave = 64;
 constexpr int kCUs = 256;

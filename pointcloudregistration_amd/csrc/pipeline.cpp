@@ -9,29 +9,6 @@
 #include <cstdio>
 #include <cstdlib>
 
-namespace pcr {
-int feature_match_impl(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
-                       const int32_t *n_src, const int32_t *n_tgt, int32_t *nn12, int32_t *nn21,
-                       hipStream_t s);
-int feature_corres_impl(const float *F, const float *G, int P, int Nmax, int Mmax, int D,
-                        const int32_t *n_src, const int32_t *n_tgt, int mutual, int ransac_n,
-                        int32_t *nn12, int32_t *corres, int32_t *n_corres, hipStream_t s);
-int corres_impl(const int32_t *nn12, const int32_t *nn21, const int32_t *n_src,
-                const int32_t *n_tgt, int P, int Nmax, int Mmax, int mutual, int ransac_n,
-                int32_t *corres, int32_t *n_corres, hipStream_t s);
-int ransac_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax,
-                const int32_t *n_src, const int32_t *n_tgt, const int32_t *corres,
-                const int32_t *n_corres, int Kmax, const uint32_t *pair_ids,
-                const pcr_ransac_params *prm, double *T_out, double *fit_out, int32_t *stats,
-                int32_t *corr_tgt, uint32_t *mask, hipStream_t s, const int32_t **order_out,
-                const GridBatch *grid_in, const int32_t *order_in, const float *perm_in);
-int icp_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax, const int32_t *n_src,
-             const int32_t *n_tgt, const double *init, const pcr_icp_params *prm, double *T_out,
-             double *fit_out, int32_t *stats, int32_t *corr_tgt, hipStream_t s, const int32_t *order_in,
-             const GridBatch *grid_in, const float *perm_in);
-int pipeline_records(const pcr_pipeline_io *io, hipStream_t s);
-}  // namespace pcr
-
 extern "C" int pcr_register_feature_ransac(const float *src_xyz, const float *tgt_xyz,
                                            const float *src_feat, const float *tgt_feat,
                                            int32_t P, int32_t Nmax, int32_t Mmax, int32_t D,

@@ -9,6 +9,7 @@
 // All sums use the deterministic 256-lane order; one 256-thread block per item.
 #include "pcr_internal.h"
 #include "geom.h"
+#include "wave.h"
 
 namespace pcr {
 namespace {
@@ -168,9 +169,7 @@ __global__ __launch_bounds__(1024) void pipeline_records_kernel(pcr_pipeline_io 
 #pragma unroll
             for (int u = 0; u < 8; ++u) acc += (double)v[u];
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-        return acc;
+        return wave_sum(acc);
     };
     const double s1 = sum(io.d1 + (size_t)p * io.N, io.N);
     const double s2 = sum(io.d2 + (size_t)p * io.M, io.M);

@@ -38,6 +38,7 @@
 #include "pcr_internal.h"
 #include "geom.h"
 #include "grid.h"
+#include "wave.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -143,12 +144,8 @@ __device__ __forceinline__ bool round_off(const RArgs &a) {
     return a.prev_active != nullptr && *a.prev_active == 0;
 }
 
-__device__ __forceinline__ int cnt_of(const int32_t *n, int p, int mx) {
-    return n ? min(max(n[p], 0), mx) : mx;
-}
-
 __device__ __forceinline__ bool pair_ok(const RArgs &a, int p, int RN) {
-    const int n = cnt_of(a.n_src, p, a.Nmax), m = cnt_of(a.n_tgt, p, a.Mmax);
+    const int n = count_of(a.n_src, p, a.Nmax), m = count_of(a.n_tgt, p, a.Mmax);
     const int K = a.n_corres ? min(max(a.n_corres[p], 0), a.Kmax) : a.Kmax;
     return K >= RN && a.d > 0.0 && n > 0 && m > 0;
 }
@@ -493,7 +490,7 @@ __device__ inline void finish_task(const RArgs &a, TaskRes *rt, int p, int r, in
             skipped = skipped || pq.flag == kSkipped;
             stopped = stopped || pq.flag == kCut;
         }
-        const int n = cnt_of(a.n_src, p, a.Nmax);
+        const int n = count_of(a.n_src, p, a.Nmax);
         const int ms = __hip_atomic_load(&rt->misses, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (skipped) out.status = kSkipped;
         else if (stopped || (lbm > 0 && ms > n - lbm)) out.status = kCut;
@@ -539,7 +536,7 @@ __global__ __launch_bounds__(kThreads) void ransac_sweep_kernel(RArgs a) {
         if (r >= maxtask) break;
         const int nt = a.ntask[p];
         if (r >= nt) continue;
-        const int n = cnt_of(a.n_src, p, a.Nmax);
+        const int n = count_of(a.n_src, p, a.Nmax);
         const int K = a.n_corres ? min(max(a.n_corres[p], 0), a.Kmax) : a.Kmax;
         const int *tk = a.tasks + (size_t)p * a.hcap;
         TaskRes *rs = a.res + (size_t)p * a.hcap;
@@ -591,8 +588,8 @@ __global__ __launch_bounds__(kThreads) void ransac_sweep_kernel(RArgs a) {
         // kernel chose), uniform over the workgroup
         const bool dense = kLds && a.grid.dense(p);
         if (kLds && sh.gp != p) {  // this pair's grid into LDS (kept while the next task is the same pair)
-            if (dense) grid_dense_to_lds(a.grid, p, cnt_of(a.n_tgt, p, a.Mmax), glds);
-            else (void)grid_to_lds4(a.grid, p, cnt_of(a.n_tgt, p, a.Mmax), glds);
+            if (dense) grid_dense_to_lds(a.grid, p, count_of(a.n_tgt, p, a.Mmax), glds);
+            else (void)grid_to_lds4(a.grid, p, count_of(a.n_tgt, p, a.Mmax), glds);
             if (tid == 0) sh.gp = p;
         }
         double Te[12];
@@ -629,7 +626,7 @@ __global__ __launch_bounds__(kThreads) void ransac_replay_kernel(RArgs a) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
     Shared &sh = *reinterpret_cast<Shared *>(dsm);
     const int p = blockIdx.x, tid = threadIdx.x;
-    const int n = cnt_of(a.n_src, p, a.Nmax), m = cnt_of(a.n_tgt, p, a.Mmax);
+    const int n = count_of(a.n_src, p, a.Nmax), m = count_of(a.n_tgt, p, a.Mmax);
     const int K = a.n_corres ? min(max(a.n_corres[p], 0), a.Kmax) : a.Kmax;
     const bool ok = pair_ok(a, p, RN);
     if (tid == 0) {

@@ -1,6 +1,7 @@
 // Workgroup-wide (1024 threads, 16 wave64) exclusive scan helpers.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "wave.h"
 
 namespace pcr {
 
@@ -22,8 +23,7 @@ __device__ inline void block_exclusive_scan_1024(int *in, int *out, int len, boo
     const int b0 = min(len, wid * seg), b1 = min(len, b0 + seg);
     int v = 0;
     for (int i = b0 + lane; i < b1; i += 64) v += in[i];
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum(v);
     if (lane == 0) warp_tot[wid] = v;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -30,10 +30,12 @@
 // ascending channel order.  Channels past C are staged as +0 (fmaf(0, 0, s)
 // = s for every s but -0, and -0 is reported as +0 anyway).
 #include "pcr_internal.h"
+#include "wave.h"
 
 namespace {
 
-typedef unsigned long long u64;
+using pcr::cdiv64, pcr::u64;
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kSimThreads = 256;
@@ -298,7 +300,6 @@ __global__ __launch_bounds__(kSelThreads) void tfmr_select(SelArgs a) {
     }
 }
 
-inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
 
 constexpr int kMaxRows = 1 << 24;   // n1, m1
 constexpr int kMaxC = 1 << 16;
@@ -313,13 +314,13 @@ int check_sizes(const char *who, int b, int n1, int m1, int c, int k) {
     PCR_REQUIRE(c <= kMaxC, PCR_ERR_ARG, "%s: c=%d too wide (max %d)", who, c, kMaxC);
     PCR_REQUIRE(k >= 1 && k <= kMaxK, PCR_ERR_ARG, "%s: k=%d outside 1..%d", who, k, kMaxK);
     PCR_REQUIRE(k <= m1, PCR_ERR_ARG, "%s: k=%d exceeds m1=%d", who, k, m1);
-    const long long blocks = (long long)b * cdivll(n1, kSimTile) * cdivll(m1, kSimTile);
+    const long long blocks = (long long)b * cdiv64(n1, kSimTile) * cdiv64(m1, kSimTile);
     PCR_REQUIRE(blocks <= 0x7fffffffLL, PCR_ERR_ARG, "%s: b=%d x n1=%d x m1=%d too large", who, b, n1, m1);
     return PCR_OK;
 }
 
 // scratch: the target tiles' lists (b,n1,ntt,k) u64, then the row keys (b,n1) u64
-long long part_words(int b, int n1, int m1, int k) { return (long long)b * n1 * cdivll(m1, kSimTile) * k; }
+long long part_words(int b, int n1, int m1, int k) { return (long long)b * n1 * cdiv64(m1, kSimTile) * k; }
 
 int check_scratch(const char *who, const void *scratch) {
     PCR_REQUIRE(scratch, PCR_ERR_ARG, "%s: null scratch", who);
@@ -350,7 +351,7 @@ extern "C" int pcr_similarity_topk(const float *fx, const float *fy, int32_t b, 
     SimArgs a;
     a.fx = fx; a.fy = fy; a.part = (u64 *)scratch;
     a.n1 = n1; a.m1 = m1; a.c = c; a.k = k;
-    a.nst = (int)cdivll(n1, kSimTile); a.ntt = (int)cdivll(m1, kSimTile);
+    a.nst = (int)cdiv64(n1, kSimTile); a.ntt = (int)cdiv64(m1, kSimTile);
     a.vec = (c % 4 == 0 && (((uintptr_t)fx | (uintptr_t)fy) & 15) == 0) ? 1 : 0;
     const dim3 grid((unsigned)((long long)b * a.nst * a.ntt));
     switch (k) {
@@ -363,7 +364,7 @@ extern "C" int pcr_similarity_topk(const float *fx, const float *fy, int32_t b, 
     PCR_LAUNCH_CHECK();
     const long long rows = (long long)b * n1;
     u64 *rowkey = a.part + part_words(b, n1, m1, k);
-    hipLaunchKernelGGL(simtopk_merge, dim3((unsigned)cdivll(rows, 256)), dim3(256), 0, s, a.part, rows, n1,
+    hipLaunchKernelGGL(simtopk_merge, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, s, a.part, rows, n1,
                        a.ntt, k, val, idx, rowkey);
     PCR_LAUNCH_CHECK();
     return PCR_OK;

@@ -19,10 +19,9 @@
 // key type and hash -- the reference's insertion sequence, hence its order --
 // and the GPU writes each voxel's row to its slot.
 #include "pcr_internal.h"
+#include "voxel_runs.h"
 
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include <climits>
 #include <cmath>
@@ -32,8 +31,6 @@
 
 namespace pcr {
 namespace {
-
-typedef unsigned long long u64;
 
 struct VArgs {
     const double *pts, *nrm, *col;
@@ -45,17 +42,7 @@ struct VArgs {
     const double *vmb;   // [nb][3] voxel_min_bound
     int sx, sy, sz, sb;  // key bit shifts (x | y | z | cloud)
     u64 *key;
-    int *iota;
 };
-
-__device__ __forceinline__ int cloud_of(const int *off, int nb, int i) {
-    int lo = 0, hi = nb - 1;  // largest b with off[b] <= i
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // one block per cloud: min / max corners (PointCloud::GetMinBound / GetMaxBound)
 __global__ __launch_bounds__(256) void vd_bbox(VArgs a) {
@@ -71,26 +58,12 @@ __global__ __launch_bounds__(256) void vd_bbox(VArgs a) {
             lo[c] = fmin(lo[c], v);
             hi[c] = fmax(hi[c], v);
         }
-    __shared__ double sl[3][4], sh[3][4];
-    __shared__ int sb[4];
-    for (int c = 0; c < 3; ++c)
-        for (int o = 32; o; o >>= 1) {
-            lo[c] = fmin(lo[c], __shfl_xor(lo[c], o, 64));
-            hi[c] = fmax(hi[c], __shfl_xor(hi[c], o, 64));
-        }
-    for (int o = 32; o; o >>= 1) bad |= __shfl_xor(bad, o, 64);
-    if ((t & 63) == 0) {
-        for (int c = 0; c < 3; ++c) { sl[c][t >> 6] = lo[c]; sh[c][t >> 6] = hi[c]; }
-        sb[t >> 6] = bad;
-    }
-    __syncthreads();
+    bad = block_bbox<double, 4>(lo, hi, bad);
     if (t != 0) return;
-    if (sb[0] | sb[1] | sb[2] | sb[3]) atomicOr(a.bad, 1);
+    if (bad) atomicOr(a.bad, 1);
     for (int c = 0; c < 3; ++c) {
-        double l = sl[c][0], h = sh[c][0];
-        for (int w = 1; w < 4; ++w) { l = fmin(l, sl[c][w]); h = fmax(h, sh[c][w]); }
-        a.bbox[6 * b + c] = l;
-        a.bbox[6 * b + 3 + c] = h;
+        a.bbox[6 * b + c] = lo[c];
+        a.bbox[6 * b + 3 + c] = hi[c];
     }
 }
 
@@ -101,34 +74,12 @@ __device__ __forceinline__ int voxel_index(double p, double vmb, double voxel) {
 __global__ void vd_key(VArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
-    const int b = cloud_of(a.off, a.nb, i);
+    const int b = segment_of(a.off, a.nb, i);
     const double *p = a.pts + 3 * (size_t)i;
     const double *m = a.vmb + 3 * b;
     const u64 ix = (u64)voxel_index(p[0], m[0], a.voxel), iy = (u64)voxel_index(p[1], m[1], a.voxel),
               iz = (u64)voxel_index(p[2], m[2], a.voxel);
     a.key[i] = ((u64)b << a.sb) | (ix << a.sx) | (iy << a.sy) | (iz << a.sz);
-    a.iota[i] = i;
-}
-
-__global__ void vd_heads(const u64 *key, int n, unsigned char *head) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) head[i] = (i == 0) || key[i] != key[i - 1];
-}
-
-// mark[first input index of voxel r] = r (the sort is stable: a run's first
-// entry is its lowest input index)
-__global__ void vd_mark(const int *start, const int *v, int V, int *mark) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < V) mark[v[start[r]]] = r;
-}
-
-struct NonNeg {
-    __device__ bool operator()(int x) const { return x >= 0; }
-};
-
-__global__ void vd_okey(const int *list, const int *start, const u64 *skey, int V, u64 *okey) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < V) okey[r] = skey[start[list[r]]];
 }
 
 // output row pos <- voxel list[outr[pos]]: sums in input order from zero
@@ -160,8 +111,6 @@ __global__ void vd_emit(VArgs a, const int *outr, int total, const int *list, co
         for (int c = 0; c < 3; ++c) oc[3 * (size_t)pos + c] = t[c] / cnt;
     }
 }
-
-inline unsigned nbits(u64 x) { return x ? 64u - (unsigned)__builtin_clzll(x) : 0u; }
 
 // Eigen::Vector3i key with Open3D's utility::hash_eigen (boost hash_combine
 // over the coefficients; std::hash<int> is the identity in libstdc++)
@@ -282,14 +231,13 @@ extern "C" int pcr_voxel_down_sample(const double *points, int32_t n, const int3
     if (N == 0) return PCR_OK;
     hipStream_t st = as_stream(stream);
     VArgs a;
-    u64 *skey, *okey;
-    int *v, *start, *mark, *list, *outr, *dcnt;
-    unsigned char *head;
+    VoxelRuns r{};  // the key carries the cloud: no ck, v2, ocloud
+    int *outr;
     WsLayout l(256);
     l.take(a.off, nb + 1); l.take(a.bbox, 6 * (size_t)nb); l.take(a.vmb, 3 * (size_t)nb); l.take(a.bad, 2);
-    l.take(a.key, N); l.take(skey, N); l.take(a.iota, N); l.take(v, N);
-    l.take(head, N); l.take(start, N + 1); l.take(mark, N); l.take(list, N);
-    l.take(okey, N); l.take(outr, N); l.take(dcnt, 2);
+    l.take(a.key, N); l.take(r.ck2, N); l.take(r.v, N);
+    l.take(r.head, N); l.take(r.start, N + 1); l.take(r.mark, N); l.take(r.list, N);
+    l.take(r.okey, N); l.take(outr, N); l.take(r.dcnt, 2);
     PCR_REQUIRE(workspace_bind(kWsVoxel, l), PCR_ERR_NOMEM, "voxel_down_sample: %s", pcr_last_error());
     a.pts = points; a.nrm = normals; a.col = colors; a.n = N; a.nb = nb;
     a.voxel = voxel_size;
@@ -336,37 +284,11 @@ extern "C" int pcr_voxel_down_sample(const double *points, int32_t n, const int3
     const dim3 gN((N + 255) / 256), blk(256);
     hipLaunchKernelGGL(vd_key, gN, blk, 0, st, a);
     PCR_LAUNCH_CHECK();
-    // stable radix sort by (cloud, voxel): input order kept inside a voxel
-    const unsigned kb = bx + by + bz + bbat;
-    size_t tb = 0, t1 = 0;
-    PCR_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, t1, a.key, skey, a.iota, v, N, 0, kb, st));
-    tb = t1;
-    PCR_HIP_CHECK(rocprim::select(nullptr, t1, rocprim::counting_iterator<int>(0), head, start, dcnt, (size_t)N, st));
-    tb = std::max(tb, t1);
-    PCR_HIP_CHECK(rocprim::select(nullptr, t1, mark, list, dcnt + 1, (size_t)N, NonNeg(), st));
-    tb = std::max(tb, t1);
-    void *tmp = workspace(kWsVoxelTmp, tb);
-    PCR_REQUIRE(tmp, PCR_ERR_NOMEM, "voxel_down_sample: %s", pcr_last_error());
-    t1 = tb;
-    PCR_HIP_CHECK(rocprim::radix_sort_pairs(tmp, t1, a.key, skey, a.iota, v, N, 0, kb, st));
-    hipLaunchKernelGGL(vd_heads, gN, blk, 0, st, skey, N, head);
-    PCR_LAUNCH_CHECK();
-    t1 = tb;
-    PCR_HIP_CHECK(rocprim::select(tmp, t1, rocprim::counting_iterator<int>(0), head, start, dcnt, (size_t)N, st));
     int V = 0;
-    PCR_HIP_CHECK(hipMemcpyAsync(&V, dcnt, sizeof(int), hipMemcpyDeviceToHost, st));
-    PCR_HIP_CHECK(hipStreamSynchronize(st));
-    PCR_HIP_CHECK(hipMemcpyAsync(start + V, &N, sizeof(int), hipMemcpyHostToDevice, st));
-    PCR_HIP_CHECK(hipMemsetAsync(mark, 0xFF, sizeof(int) * N, st));
-    const dim3 gV((V + 255) / 256);
-    hipLaunchKernelGGL(vd_mark, gV, blk, 0, st, start, v, V, mark);
-    PCR_LAUNCH_CHECK();
-    t1 = tb;
-    PCR_HIP_CHECK(rocprim::select(tmp, t1, mark, list, dcnt + 1, (size_t)N, NonNeg(), st));
-    hipLaunchKernelGGL(vd_okey, gV, blk, 0, st, list, start, skey, V, okey);
-    PCR_LAUNCH_CHECK();
+    const int rc = voxel_runs(a.key, bx + by + bz + bbat, nullptr, 0, N, r, kWsVoxelTmp, "voxel_down_sample", st, &V);
+    if (rc != PCR_OK) return rc;
     std::vector<u64> hk(V);
-    PCR_HIP_CHECK(hipMemcpyAsync(hk.data(), okey, sizeof(u64) * V, hipMemcpyDeviceToHost, st));
+    PCR_HIP_CHECK(hipMemcpyAsync(hk.data(), r.okey, sizeof(u64) * V, hipMemcpyDeviceToHost, st));
     PCR_HIP_CHECK(hipStreamSynchronize(st));
     // per cloud: the map's iteration order (voxels in first-occurrence order);
     // clouds are independent, so their replays run on host threads
@@ -404,7 +326,7 @@ extern "C" int pcr_voxel_down_sample(const double *points, int32_t n, const int3
     }
     const int total = (int)hout.size();
     PCR_HIP_CHECK(hipMemcpyAsync(outr, hout.data(), sizeof(int) * total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(vd_emit, dim3((total + 255) / 256), blk, 0, st, a, outr, total, list, start, v,
+    hipLaunchKernelGGL(vd_emit, dim3((total + 255) / 256), blk, 0, st, a, outr, total, r.list, r.start, r.v,
                        out_points, normals ? out_normals : nullptr, colors ? out_colors : nullptr);
     PCR_LAUNCH_CHECK();
     PCR_HIP_CHECK(hipStreamSynchronize(st));  // hout is a host temporary

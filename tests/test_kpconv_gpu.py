@@ -150,6 +150,28 @@ def test_subsample_edges(K, oracle, map_order):
         K.subsample_batch(p, [500], sampleDl=0.2, method="centroids")
 
 
+def test_subsample_keys_wider_than_one_sort_key(K, oracle, map_order):
+    """64-bit voxel keys in two clouds: with the cloud bit the (cloud, key)
+    composite needs 65 bits, so the run builder sorts in two stable passes."""
+    rng = np.random.default_rng(5)
+    clouds = []
+    for _ in range(2):
+        c = rng.uniform(-1100, 1100, (300, 3)).astype(np.float32)
+        assert len(np.unique(c, axis=0)) == 300
+        clouds.append(np.concatenate([c, c[:100]]))  # exact copies: voxels of two points
+    p = np.concatenate(clouds)
+    f = rng.standard_normal((800, 3)).astype(np.float32)
+    keys = [oracle.voxel_keys(c, 0.001) for c in clouds]
+    assert all(int(k.max()).bit_length() == 64 for k in keys)
+    assert max(np.unique(k, return_counts=True)[1].max() for k in keys) > 1
+    for mp in (0, 25):
+        got = K.subsample_batch(p, [400, 400], features=f, sampleDl=0.001, max_p=mp)
+        want = oracle.grid_subsample(p, [400, 400], 0.001, features=f, max_p=mp, order=map_order)
+        assert len(got) == len(want) == 3
+        for x, y in zip(got, want):
+            assert np.array_equal(x, y), mp
+
+
 def test_batch_query_random_against_reference(K, oracle):
     R = _ref()
     rng = np.random.default_rng(8)
