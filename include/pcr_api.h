@@ -956,6 +956,74 @@ int pcr_kpconv_forward(const float *q_pts, const float *s_pts, const float *s_fe
 int pcr_neighbor_max(const float *feats, const void *inds, int32_t index_width, int32_t n, int32_t m,
                      int32_t k, int32_t c, float *out, pcr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Softmax attention without the score matrix: NgeNet's Cross_Attention and
+ * overlap scores (c2p-net/ngenet/models/information_interactive.py:165-214,
+ * NgeNet.py:170-179) and ROPNet's OverlapAttentionBlock
+ * (ROPNet/src/models/TFMR.py:76-106), for inference.  No allocation
+ * proportional to n m is made or needed.  The f64 restatement with the derived
+ * bound is tests/attention_ref.py.
+ *
+ * Layout.  Every tensor is f32, channel-major with UNIT TOKEN STRIDE: element
+ *   (batch, head, channel, token) of x is x[batch x_sb + head x_sh + channel x_sc
+ *   + token], the strides in elements.  That takes the (B, dim, nhead, N) view of
+ *   a Conv1d output (x_sh = N, x_sc = nhead N) and column slices of a wider
+ *   tensor without a copy.  Strides are not checked: every element they name
+ *   must lie in the tensor.  out must not overlap an input.
+ *
+ * pcr_attention_forward:
+ *   out[b,h,c,i] = sum_j P_ij v[b,h,c,j],  P = softmax_j(scale sum_e q[b,h,e,i] k[b,h,e,j])
+ *   with i < n queries, j < m keys, e < d, c < dv.
+ * pcr_offset_attention_forward (no heads):
+ *   a_ij = r_i sum_e q[b,e,i] k[b,e,j]   (row_scale r: (b, n) with batch stride
+ *                                         r_sb, unit stride over i; null: r = 1)
+ *   P = softmax_j(a),  c_j = sum_i P_ij,
+ *   out[b,ch,j] = (sum_i v[b,ch,i] P_ij) / (1e-9f + c_j)       i, j < n.
+ *
+ * Numerics.  f32 throughout.  Scores are the f32 MFMA's fmaf chain over e
+ *   ascending (v_mfma_f32_32x32x2_f32), times scale (r_i), each rounded.  Keys
+ *   are walked in tiles of 32 with an online softmax: per tile the running
+ *   maximum is raised, the sum and the accumulators are multiplied by
+ *   expf(old max - new max) and the tile's weights expf(score - max) are added;
+ *   expf is the library's (1 ulp), there is no deferred rescale.  P V is a second
+ *   f32 MFMA chain over j ascending (dv <= 4: separately rounded multiply-adds),
+ *   the quotient one f32 division.  Where b h ceil(n / 128) ceil(dv / 64) <= 64
+ *   and m > 224 (8 tiles) the keys are split into up to 16 runs of whole tiles whose
+ *   (accumulator, maximum, sum) partials go through `scratch` and are combined in
+ *   run order.  The offset form's sweep 1 computes the rows' maxima and sums
+ *   the same way into `scratch`; sweep 2 forms P_ij = expf(a_ij - max_i) *
+ *   (1 / sum_i) and accumulates c_j and the numerator over i ascending.
+ *   Every order depends on the sizes only and there are no atomics: two calls
+ *   return the same bytes, and a batch element's result does not depend on b
+ *   as long as the split (a function of b h n m dv) is the same.
+ *   A key past m (a row past n) has weight exactly +0; no exp sees -inf - -inf.
+ *   Bound against the f64 restatement: tests/attention_ref.py.
+ * Non-finite inputs: the rows (columns) they touch are unspecified, possibly
+ *   NaN; every access stays in range and every kernel terminates.
+ * Limits.  b >= 0, h >= 1, d and dv in 1 .. 256, n in 0 .. 2^24, m in 1 .. 2^24.
+ *   Anything else, or a null pointer, returns PCR_ERR_ARG with its message before
+ *   any device work; b = 0 or n = 0 returns PCR_OK without a launch (m = 0 is
+ *   an error).
+ * Scratch.  pcr_attention_scratch_bytes: 0 unless the keys are split, then
+ *   splits b h (dv + 2) n floats (at most 16 (1 + 2 / dv) times the output;
+ *   the split needs the grid to be at most 64 workgroups).  A null scratch is
+ *   accepted when it is 0.  pcr_offset_attention_scratch_bytes: 8 b n bytes.
+ *   Both return -1 on bad sizes; scratch must be 16-byte aligned.
+ * Both calls are asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+int64_t pcr_attention_scratch_bytes(int32_t b, int32_t h, int32_t n, int32_t m, int32_t d, int32_t dv);
+int pcr_attention_forward(const float *q, int64_t q_sb, int64_t q_sh, int64_t q_sc, const float *k,
+                          int64_t k_sb, int64_t k_sh, int64_t k_sc, const float *v, int64_t v_sb,
+                          int64_t v_sh, int64_t v_sc, float *out, int64_t o_sb, int64_t o_sh,
+                          int64_t o_sc, int32_t b, int32_t h, int32_t n, int32_t m, int32_t d,
+                          int32_t dv, float scale, void *scratch, pcr_stream_t stream);
+int64_t pcr_offset_attention_scratch_bytes(int32_t b, int32_t n, int32_t d, int32_t dv);
+int pcr_offset_attention_forward(const float *q, int64_t q_sb, int64_t q_sc, const float *k, int64_t k_sb,
+                                 int64_t k_sc, const float *v, int64_t v_sb, int64_t v_sc,
+                                 const float *row_scale, int64_t r_sb, float *out, int64_t o_sb,
+                                 int64_t o_sc, int32_t b, int32_t n, int32_t d, int32_t dv,
+                                 void *scratch, pcr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

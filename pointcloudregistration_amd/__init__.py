@@ -13,15 +13,18 @@ reference's operator interfaces:
                  (similarity, row selection, weights and correspondences)
   cpd            probreg.cpd's RigidCPD / AffineCPD / NonRigidCPD (Coherent
                  Point Drift) with a matrix-free E-step, and a batched loop
+  attention      the softmax attention of NgeNet's Cross_Attention and overlap
+                 scores and of ROPNet's OverlapAttentionBlock, fused (no score
+                 matrix), with drop-in modules and fuse()
 """
 from ._lib import PcrError, load as load_library  # noqa: F401
 
-__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd"]
+__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd", "attention"]
 
 
 def __getattr__(name):
     # the op modules import torch; the package itself (ABI loader) does not
-    if name in ("grouping", "matching", "cpd"):
+    if name in ("grouping", "matching", "cpd", "attention"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -112,6 +112,10 @@ SIGNATURES = {
     "pcr_kpconv_forward": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _i32, _i32, _i32, _f32, _i32, _p, _p,
                            _p],
     "pcr_neighbor_max": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p],
+    "pcr_attention_forward": [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64,
+                              _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p],
+    "pcr_offset_attention_forward": [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, _i64,
+                                     _i32, _i32, _i32, _i32, _p, _p],
 }
 
 
@@ -161,6 +165,10 @@ def load():
         lib.pcr_tfmr_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32]
         lib.pcr_cpd_scratch_bytes.restype = _i64
         lib.pcr_cpd_scratch_bytes.argtypes = [_i32, _i32, _i32]
+        lib.pcr_attention_scratch_bytes.restype = _i64
+        lib.pcr_attention_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32]
+        lib.pcr_offset_attention_scratch_bytes.restype = _i64
+        lib.pcr_offset_attention_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32]
         lib.pcr_shutdown.restype = ctypes.c_int
         lib.pcr_shutdown.argtypes = []
         for name, args in SIGNATURES.items():
@@ -179,7 +187,8 @@ def exported_symbols():
     return ["pcr_last_error", "pcr_version", "pcr_workspace_release", "pcr_profile_enable", "pcr_profile_read",
             "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_featnn_image_chunks", "pcr_ndp_train_partial_floats", "pcr_ndp_chamfer_scratch_bytes",
             "pcr_ndp_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words", "pcr_ndp_chamfer_max_points",
-            "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_shutdown"] + \
+            "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_attention_scratch_bytes",
+            "pcr_offset_attention_scratch_bytes", "pcr_shutdown"] + \
         list(SIGNATURES)
 
 
