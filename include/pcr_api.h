@@ -1024,6 +1024,79 @@ int pcr_offset_attention_forward(const float *q, int64_t q_sb, int64_t q_sc, con
                                  int64_t o_sc, int32_t b, int32_t n, int32_t d, int32_t dv,
                                  void *scratch, pcr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * DIP's PointNet descriptor forward (dip/network.py:50-100) in eval mode, for
+ * inference: per patch x (3, P)
+ *   T-net (tnet = 1):  3 -> 128 -> 256, max over points, -> 128 -> 9, + I = T
+ *   xtrans = T x                                 (tnet = 0: xtrans = x)
+ *   main:  3 -> 128 -> 256, max and argmax over points (mx, amx),
+ *          -> 128 (hid) -> dim (f), l2-normalised where l2norm = 1.
+ * Every layer but the last of a branch is followed by ReLU; BatchNorm (eval)
+ * is folded into the weights by the caller.  No allocation proportional to
+ * B P C is made or needed: no per-point activation reaches global memory.  The
+ * f64 restatement with the derived bounds is tests/pointnet_ref.py.
+ *
+ * Weights.  pcr_pointnet_layers holds one branch: w1 (128, 3), w2 (256, 128),
+ *   w3 (128, 256), w4 (dim, 128) -- (9, 128) in the T-net -- row-major (out, in),
+ *   and the biases b1 .. b4; f32 device pointers, folded (W' = W s, b' = (b -
+ *   mean) s + beta with s = gamma / sqrt(var + eps)).  pcr_pointnet_weights is a
+ *   HOST struct of the two branches; `stn` is not read when tnet = 0.
+ * Input.  Element (b, coord, point) of x is x[b x_sb + coord x_sc + point x_sp],
+ *   strides in elements: a contiguous (B, 3, P) tensor and the transposed view
+ *   of a (B, P, 3) one both go in without a copy.  Strides are not checked.
+ * Outputs.  f (B, dim), mx (B, 256) required; amx (B, 256) int32, hid (B, 128)
+ *   (fc1's post-ReLU output of the main branch), trans (B, 9) (written when
+ *   tnet = 1 only) and xtrans (B, 3, P) may be null.  All contiguous.
+ *
+ * Numerics.  f32 throughout.
+ *   Layer.  y[o] = b'[o] + sum_c W'[o][c] h[c] is one f32 fmaf chain over c
+ *     ascending that STARTS from the bias: fmaf(W'[o][2], h[2], fmaf(W'[o][1],
+ *     h[1], fmaf(W'[o][0], h[0], b'[o]))) ...  The 3-input layers run on the
+ *     VALU (fmaf), every other layer on v_mfma_f32_32x32x2_f32 with the bias as
+ *     the accumulator's initial value (k-step t adds channels 2 t, then 2 t + 1).
+ *     ReLU is max(y, +0).
+ *   Pool.  mx[o] is the maximum over points 0 .. P - 1 of conv2's post-ReLU
+ *     output, amx[o] the lowest point index attaining it.  Points are walked in
+ *     tiles of 64; those of a partly filled tile past P do not take part.
+ *   Transform.  trans = t + I, one f32 add per element (the zeros of I too);
+ *     xtrans[r][p] = (T[r][0] x[0][p] + T[r][1] x[1][p]) + T[r][2] x[2][p],
+ *     every product and sum rounded.
+ *   Normalisation.  f / max(sqrt(sum_o f[o]^2), 1e-12f): the squares, each
+ *     rounded, are added to +0 over o ascending, one rounded add each; sqrt and
+ *     the division are correctly rounded.
+ *   Order.  Every order depends on (P, dim, tnet, l2norm) only and there are
+ *     no atomics: two calls return the same bytes, and a patch's bytes do not
+ *     depend on B or on its position in the batch.
+ *   Composition.  A tnet = 1 call returns the same bytes as: (1) this entry
+ *     with the T-net's four layers as `main`, tnet = 0, l2norm = 0, dim = 9;
+ *     (2) trans = f + I and the transform above in f32 on the host; (3) this
+ *     entry with the main layers, tnet = 0, on that xtrans.
+ * Non-finite inputs: the patch's values are unspecified; every access stays in
+ *   range and every kernel terminates.
+ * Limits.  B in 0 .. 2^20, P in 1 .. 4096, dim in 1 .. 256.  Anything else, or a
+ *   null required pointer (x, f, mx, w, a layer of a branch in use, scratch
+ *   when tnet = 1), returns PCR_ERR_ARG with its message before any device work;
+ *   B = 0 returns PCR_OK without a launch.
+ * Scratch.  pcr_pointnet_scratch_bytes: 0 when tnet = 0, else B (256 + 16) floats
+ *   (the T-net's pooled vector and matrix), rounded up to 256 bytes; -1 on bad
+ *   sizes.  Scratch must be 16-byte aligned.
+ * The call is asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+typedef struct pcr_pointnet_layers {
+    const float *w1, *b1, *w2, *b2, *w3, *b3, *w4, *b4;
+} pcr_pointnet_layers;
+
+typedef struct pcr_pointnet_weights {
+    pcr_pointnet_layers stn;   /* the T-net: w4 (9, 128), b4 (9) */
+    pcr_pointnet_layers main;  /* w4 (dim, 128), b4 (dim) */
+} pcr_pointnet_weights;
+
+int64_t pcr_pointnet_scratch_bytes(int32_t B, int32_t dim, int32_t tnet);
+int pcr_pointnet_forward(const float *x, int64_t x_sb, int64_t x_sc, int64_t x_sp, int32_t B, int32_t P,
+                         const pcr_pointnet_weights *w, int32_t dim, int32_t tnet, int32_t l2norm, float *f,
+                         float *mx, int32_t *amx, float *hid, float *trans, float *xtrans, void *scratch,
+                         pcr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

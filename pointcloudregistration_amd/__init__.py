@@ -16,15 +16,18 @@ reference's operator interfaces:
   attention      the softmax attention of NgeNet's Cross_Attention and overlap
                  scores and of ROPNet's OverlapAttentionBlock, fused (no score
                  matrix), with drop-in modules and fuse()
+  pointnet       DIP's PointNetFeature forward (T-net, both MLPs, max-pool,
+                 heads, l2 norm) fused for inference: fold / prepare /
+                 describe, FusedPointNetFeature and fuse()
 """
 from ._lib import PcrError, load as load_library  # noqa: F401
 
-__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd", "attention"]
+__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd", "attention", "pointnet"]
 
 
 def __getattr__(name):
     # the op modules import torch; the package itself (ABI loader) does not
-    if name in ("grouping", "matching", "cpd", "attention"):
+    if name in ("grouping", "matching", "cpd", "attention", "pointnet"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

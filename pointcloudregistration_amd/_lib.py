@@ -48,6 +48,16 @@ class IcpParams(ctypes.Structure):
                 ("relative_rmse", _f64), ("max_iteration", _i32), ("reserved", _i32)]
 
 
+class PointNetLayers(ctypes.Structure):
+    """pcr_pointnet_layers (include/pcr_api.h): one branch's folded weights, device pointers."""
+    _fields_ = [(n, _p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4")]
+
+
+class PointNetWeights(ctypes.Structure):
+    """pcr_pointnet_weights (include/pcr_api.h)."""
+    _fields_ = [("stn", PointNetLayers), ("main", PointNetLayers)]
+
+
 _rp = ctypes.POINTER(RansacParams)
 _ip = ctypes.POINTER(IcpParams)
 
@@ -116,6 +126,8 @@ SIGNATURES = {
                               _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p],
     "pcr_offset_attention_forward": [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, _i64,
                                      _i32, _i32, _i32, _i32, _p, _p],
+    "pcr_pointnet_forward": [_p, _i64, _i64, _i64, _i32, _i32, ctypes.POINTER(PointNetWeights), _i32, _i32, _i32,
+                             _p, _p, _p, _p, _p, _p, _p, _p],
 }
 
 
@@ -169,6 +181,8 @@ def load():
         lib.pcr_attention_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32]
         lib.pcr_offset_attention_scratch_bytes.restype = _i64
         lib.pcr_offset_attention_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32]
+        lib.pcr_pointnet_scratch_bytes.restype = _i64
+        lib.pcr_pointnet_scratch_bytes.argtypes = [_i32, _i32, _i32]
         lib.pcr_shutdown.restype = ctypes.c_int
         lib.pcr_shutdown.argtypes = []
         for name, args in SIGNATURES.items():
@@ -188,7 +202,7 @@ def exported_symbols():
             "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_featnn_image_chunks", "pcr_ndp_train_partial_floats", "pcr_ndp_chamfer_scratch_bytes",
             "pcr_ndp_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words", "pcr_ndp_chamfer_max_points",
             "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_attention_scratch_bytes",
-            "pcr_offset_attention_scratch_bytes", "pcr_shutdown"] + \
+            "pcr_offset_attention_scratch_bytes", "pcr_pointnet_scratch_bytes", "pcr_shutdown"] + \
         list(SIGNATURES)
 
 

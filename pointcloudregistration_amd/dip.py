@@ -4,7 +4,8 @@
                   voxel_down_sample(1.0) (:73-74) -> np.random.choice of 2048
                   points per cloud (:80-87) -> LRF patches of every sampled point,
                   draws interleaved frag1 i / frag2 i (:109-114) -> descriptor
-                  network in batches of 500 (:128-147; stays PyTorch, passed in)
+                  network in batches of 500 (:128-147; passed in: a PyTorch module,
+                  or pointnet.fuse(net) to run it on libpcr too)
                   -> 5th-percentile filter on |mx| (:149-156) -> feature RANSAC at
                   1.5 voxel (:37-53, :178)
   percentile_keep the filter of :149-153
@@ -70,7 +71,7 @@ def demo_register(source, target, net, voxel_size=1.0, lrf_kernel=3.0 * np.sqrt(
                   patch_size=256, pts_to_sample=2048, perc=5, batch_size=500, seed=0):
     """One pair through dip/demo.py:64-178.  `net(patches (B,3,ps) f32 cuda) ->
     (f (B,dim), mx (B,256), ...)` is the descriptor network (PointNetFeature in the
-    reference).  Returns a dict with the RANSAC result and the intermediates
+    reference; pointnet.fuse(net) is its fused form).  Returns a dict with the RANSAC result and the intermediates
     (down-sampled clouds, sample indices, patches, descriptors, keep masks)."""
     pcd1, pcd2 = PointCloud(np.asarray(source)), PointCloud(np.asarray(target))
     pcd1.paint_uniform_color(GREY)
