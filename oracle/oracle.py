@@ -76,6 +76,8 @@ def _setup_sigs():
     L.oracle_det_log.argtypes = [c.c_double]
     L.oracle_est_k.restype = c.c_double
     L.oracle_est_k.argtypes = [c.c_double, c.c_int, c.c_double]
+    L.oracle_est_k_iters.restype = c.c_int
+    L.oracle_est_k_iters.argtypes = [c.c_double]
     L.oracle_radius_thr.restype = c.c_double
     L.oracle_radius_thr.argtypes = [c.c_double]
     L.oracle_procrustes_batch.argtypes = [c.c_void_p] * 3 + [c.c_int, c.c_int, c.c_int, c.c_double, c.c_void_p]
@@ -126,6 +128,12 @@ def det_log(x):
 
 def est_k(w, n, conf):
     return L().oracle_est_k(float(w), int(n), float(conf))
+
+
+def est_k_iters(kd):
+    """The bound est_k(...) as the loop's int (for kd below the current bound):
+    ceil(kd) when positive, else 0 -- never a conversion of -inf."""
+    return L().oracle_est_k_iters(float(kd))
 
 
 def philox(seed, pair, itr, block=0):

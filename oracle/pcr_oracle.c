@@ -552,6 +552,12 @@ double oracle_est_k(double w, int n, double confidence)
     return oracle_det_log(1.0 - confidence) / oracle_det_log(1.0 - pw);
 }
 
+/* The bound as the loop's int.  Called only with kd < est_k (an int, at most   */
+/* max_iter), so ceil(kd) fits whenever kd > 0; a bound at or below zero --    */
+/* -inf when 1 - w^n rounds to 1.0 and det_log gives 0 -- is 0: the loop ends  */
+/* after the accepting iteration.  (A cast of -inf to int is undefined.)      */
+int oracle_est_k_iters(double kd) { return kd > 0.0 ? (int)ceil(kd) : 0; }
+
 static void to_double3(const float *src, int n, double *dst)
 {
     for (int i = 0; i < 3 * n; i++) dst[i] = (double)src[i];
@@ -619,7 +625,7 @@ static int ransac_core(const double *S, int n, const double *Tg, int m, const og
                 if (d2_3(p, Tg + 3 * corres[2 * k + 1]) < dd) cin++;
             }
             const double kd = oracle_est_k((double)cin / (double)K, rn, conf);
-            if (kd < (double)est_k) est_k = (int)ceil(kd);
+            if (kd < (double)est_k) est_k = oracle_est_k_iters(kd);
         }
     }
     memcpy(o->T, bestT, sizeof(bestT));

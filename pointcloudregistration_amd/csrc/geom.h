@@ -64,6 +64,11 @@ __device__ inline double est_k_bound(double w, int n, double conf) {
     return det_log(1.0 - conf) / det_log(1.0 - pw);
 }
 
+// the bound as the loop's int, for kd below the current (int) bound: ceil(kd)
+// then fits when kd > 0; at or below zero (-inf when 1 - w^n rounds to 1.0) it is
+// 0 and the loop ends after the accepting iteration (oracle_est_k_iters)
+__device__ inline int est_k_iters(double kd) { return kd > 0.0 ? (int)__builtin_ceil(kd) : 0; }
+
 // ---- rigid transforms ([R|t] row-major 3x4) ---------------------------------
 __device__ __forceinline__ void xform12(const double *T, double px, double py, double pz,
                                         double &ox, double &oy, double &oz) {

@@ -282,7 +282,7 @@ __device__ inline bool apply_result(RState &s, int itr, const TaskRes &r, const 
         if (T)
             for (int k = 0; k < 12; ++k) s.bestT[k] = T[k];
         const double kd = est_k_bound((double)r.cin / (double)K, RN, conf);
-        if (kd < (double)s.est_k) s.est_k = (int)__builtin_ceil(kd);
+        if (kd < (double)s.est_k) s.est_k = est_k_iters(kd);
         return true;
     }
     return false;
