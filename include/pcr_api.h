@@ -1097,6 +1097,105 @@ int pcr_pointnet_forward(const float *x, int64_t x_sb, int64_t x_sc, int64_t x_s
                          float *mx, int32_t *amx, float *hid, float *trans, float *xtrans, void *scratch,
                          pcr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * The consumers of the grouping front ends, fused for inference: the edge conv
+ * of NgeNet's GCN (c2p-net/ngenet/models/information_interactive.py:107-130)
+ * and the grouped local-feature MLP behind NgeNet's PPF (:26-84) and ROPNet's
+ * LocalFeatue (ROPNet/src/models/TFMR.py:17-73).  Both norms take their
+ * statistics over the whole cloud (no running statistics), so nothing folds
+ * into the weights; no allocation proportional to n kk c or n K c is made or
+ * needed.  The f64 restatement with the derived bounds is tests/groupmlp_ref.py.
+ *
+ * pcr_edge_conv: per cloud, point i, neighbour j = idx[i][e] (e < kk) and
+ *   output channel o, with W = [Wa | Wb] of shape (co, 2 c) row-major, no bias:
+ *     y[i][e][o] = sum_k Wa[o][k] f[i][k] + sum_k Wb[o][k] (f[j][k] - f[i][k])
+ *     out[i][o]  = max_e lrelu(instance_norm(y)[i][e][o])
+ *   the norm over all n kk values of (cloud, channel), biased variance, no affine.
+ * pcr_group_mlp: x (b, n, K, cin) channels last (pcr_group_ppf's layout with
+ *   channels_first = 0); `layers` (1 .. 3) times
+ *     y_l = W_l h_{l-1}  (no bias),  h_l = act(norm(y_l)),  h_0 = x
+ *   the norm over all n K values of (cloud, channel) (group = 1: InstanceNorm2d)
+ *   or of (cloud, 32 consecutive channels) (group = 32: GroupNorm(c / 32, c)),
+ *   with the optional affine gamma, beta (c_l) (null: 1, 0);
+ *     out[i][o] = max_k h_L[i][k][o].
+ *   act(v) = v for v > 0, else slope v (slope = 0: +0, ReLU).
+ *
+ * How it is computed (what the contract fixes).
+ *   Layer.  Every y is ONE f32 fmaf chain over the input channels ascending from
+ *     +0: layer 1 of the MLP on the VALU, every other product on
+ *     v_mfma_f32_32x32x2_f32 (k-step t adds channels 2 t, then 2 t + 1).
+ *   Edge conv.  P[i][o] = chain over Wa[o][.] f[i][.], Q[i][o] = chain over
+ *     Wb[o][.] f[i][.]; R = P - Q (one f32 subtraction); y = R[i] + Q[j] (one f32
+ *     add), the row's kk neighbours in order.  An index is clamped into [0, n)
+ *     as pcr_edge_features does.
+ *   Statistics.  Per (cloud, channel) sum y and sum y^2 are f64 sums of the f32
+ *     y (the square formed in f64, exact): rows in ascending order within a
+ *     tile; the tiles' partials are added in 16 runs of ceil(tiles / 16)
+ *     consecutive tiles, each in ascending tile order, and the runs' sums in
+ *     run order; with group = 32 the 32 channel sums are then added over
+ *     channels ascending.  mean = S / m,
+ *     var = S2 / m - mean^2 (clamped at 0), rstd = 1 / sqrt(var + eps), all f64.
+ *   Coefficients.  a = gamma rstd, b = beta - mean (gamma rstd), computed in
+ *     f64 and each rounded ONCE to f32.  h = act(fmaf(y, a, b)).
+ *   Pool.  y -> act(fmaf(y, a, b)) is monotone, rounding included, so
+ *     out = act(fmaf(a >= 0 ? max y : min y, a, b)) over the neighbours equals
+ *     the max of the activated values bit for bit; only max and min of the last
+ *     layer's y are kept per (point, channel).
+ *   Tiles.  The MLP walks the cloud's n K rows in tiles of 64: K <= 64 puts
+ *     floor(64 / K) whole points in a tile, K > 64 splits a point into
+ *     ceil(K / 64) tiles.  The edge conv's statistics tile is 8 points.  The map
+ *     depends on (n, K) only, never on the grid or on b; rows of a partly
+ *     filled tile take no part in the statistics or the pool.  No atomics.
+ *     A pass recomputes the layers before it (pass l: layers 1 .. l), with the
+ *     same code, from finished coefficients.
+ *   Consequences: two calls return the same bytes; a cloud's bytes do not depend
+ *     on b or on its position in the batch; the y_1, y_2 of a 3-layer call equal
+ *     byte for byte those of the 1- and 2-layer calls on the same leading layers.
+ * Layout.  feats: element (batch, point, channel) is feats[batch f_sb + point
+ *   f_sp + channel f_sc] (strides in elements, not checked), so (b, n, c) and
+ *   (b, c, n) tensors both go in without a copy.  idx (b, n, kk) int32, x, the
+ *   weights (c_l, c_{l-1}) row-major and every output are contiguous.  out is
+ *   (b, n, c_L), or (b, c_L, n) with channels_first = 1.
+ * Optional outputs (null in normal use; each is written by the stage itself):
+ *   rq (b, n, 2 co): R | Q of the edge conv; y[l] (b, n, K, c_l): the pre-norm
+ *   activations; stats (b, co, 2) / stats[l] (b, c_l / group, 2): f64 (mean, var).
+ * Non-finite inputs: the clouds they touch are unspecified; every access stays
+ *   in range and every kernel terminates.
+ * Limits.  b in 0 .. 65535, n in 2 .. 2^20, kk in 1 .. 63, K in 1 .. 128, cin in
+ *   1 .. 16, every width (c, co, c_l) a multiple of 32 in 32 .. 512, group 1 or
+ *   32, eps >= 0.  Anything else, or a null required pointer, returns
+ *   PCR_ERR_ARG with its message before any device work; b = 0 returns PCR_OK
+ *   without a launch.
+ * Scratch (16-byte aligned; the functions return -1 on bad sizes, the text in
+ *   pcr_last_error).  pcr_edge_conv_scratch_bytes: R | Q, max, min (4 b n co
+ *   floats), a | b (2 b co floats) and the partials (2 b ceil(n / 8) co
+ *   doubles): no term in kk.  pcr_group_mlp_scratch_bytes: a | b per layer,
+ *   max and min (2 b n ceil(K / 64) c_L floats) and the per-tile partials
+ *   (2 b tiles max c_l doubles, tiles = ceil(n / floor(64 / K)) or n ceil(K / 64)):
+ *   the only terms in K, one 64th of a materialised activation.
+ * Both calls are asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+typedef struct pcr_group_mlp_net {
+    int32_t layers;         /* 1 .. 3 */
+    int32_t width[3];       /* c_l */
+    const float *w[3];      /* (c_l, c_{l-1}), c_0 = cin */
+    const float *gamma[3];  /* (c_l) or null */
+    const float *beta[3];   /* (c_l) or null */
+    float *y[3];            /* optional (b, n, K, c_l) */
+    double *stats[3];       /* optional (b, c_l / group, 2) */
+} pcr_group_mlp_net;        /* a HOST struct of device pointers */
+
+int64_t pcr_edge_conv_scratch_bytes(int32_t b, int32_t n, int32_t kk, int32_t c, int32_t co);
+int pcr_edge_conv(const float *feats, int64_t f_sb, int64_t f_sp, int64_t f_sc, const int32_t *idx, int32_t b,
+                  int32_t n, int32_t kk, int32_t c, int32_t co, const float *w, double eps, float slope,
+                  int32_t channels_first, float *out, float *rq, double *stats, void *scratch,
+                  pcr_stream_t stream);
+int64_t pcr_group_mlp_scratch_bytes(int32_t b, int32_t n, int32_t K, int32_t layers, int32_t c1, int32_t c2,
+                                    int32_t c3);
+int pcr_group_mlp(const float *x, int32_t b, int32_t n, int32_t K, int32_t cin, const pcr_group_mlp_net *net,
+                  int32_t group, double eps, float slope, int32_t channels_first, float *out, void *scratch,
+                  pcr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,15 +19,19 @@ reference's operator interfaces:
   pointnet       DIP's PointNetFeature forward (T-net, both MLPs, max-pool,
                  heads, l2 norm) fused for inference: fold / prepare /
                  describe, FusedPointNetFeature and fuse()
+  groupmlp       what consumes grouping's PPF group and k-NN graph: the edge
+                 conv of NgeNet's GCN and the grouped local-feature MLP of
+                 NgeNet's PPF and ROPNet's LocalFeatue, fused (no per-neighbour
+                 activation), with GCN / PPF / LocalFeature modules and fuse()
 """
 from ._lib import PcrError, load as load_library  # noqa: F401
 
-__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd", "attention", "pointnet"]
+__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd", "attention", "pointnet", "groupmlp"]
 
 
 def __getattr__(name):
     # the op modules import torch; the package itself (ABI loader) does not
-    if name in ("grouping", "matching", "cpd", "attention", "pointnet"):
+    if name in ("grouping", "matching", "cpd", "attention", "pointnet", "groupmlp"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

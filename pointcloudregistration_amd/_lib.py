@@ -58,6 +58,12 @@ class PointNetWeights(ctypes.Structure):
     _fields_ = [("stn", PointNetLayers), ("main", PointNetLayers)]
 
 
+class GroupMlpNet(ctypes.Structure):
+    """pcr_group_mlp_net (include/pcr_api.h): a host struct of device pointers."""
+    _fields_ = [("layers", _i32), ("width", _i32 * 3), ("w", _p * 3), ("gamma", _p * 3), ("beta", _p * 3),
+                ("y", _p * 3), ("stats", _p * 3)]
+
+
 _rp = ctypes.POINTER(RansacParams)
 _ip = ctypes.POINTER(IcpParams)
 
@@ -128,6 +134,9 @@ SIGNATURES = {
                                      _i32, _i32, _i32, _i32, _p, _p],
     "pcr_pointnet_forward": [_p, _i64, _i64, _i64, _i32, _i32, ctypes.POINTER(PointNetWeights), _i32, _i32, _i32,
                              _p, _p, _p, _p, _p, _p, _p, _p],
+    "pcr_edge_conv": [_p, _i64, _i64, _i64, _p, _i32, _i32, _i32, _i32, _i32, _p, _f64, _f32, _i32, _p, _p, _p, _p,
+                      _p],
+    "pcr_group_mlp": [_p, _i32, _i32, _i32, _i32, ctypes.POINTER(GroupMlpNet), _i32, _f64, _f32, _i32, _p, _p, _p],
 }
 
 
@@ -183,6 +192,10 @@ def load():
         lib.pcr_offset_attention_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32]
         lib.pcr_pointnet_scratch_bytes.restype = _i64
         lib.pcr_pointnet_scratch_bytes.argtypes = [_i32, _i32, _i32]
+        lib.pcr_edge_conv_scratch_bytes.restype = _i64
+        lib.pcr_edge_conv_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32]
+        lib.pcr_group_mlp_scratch_bytes.restype = _i64
+        lib.pcr_group_mlp_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, _i32]
         lib.pcr_shutdown.restype = ctypes.c_int
         lib.pcr_shutdown.argtypes = []
         for name, args in SIGNATURES.items():
@@ -202,7 +215,8 @@ def exported_symbols():
             "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_featnn_image_chunks", "pcr_ndp_train_partial_floats", "pcr_ndp_chamfer_scratch_bytes",
             "pcr_ndp_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words", "pcr_ndp_chamfer_max_points",
             "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_attention_scratch_bytes",
-            "pcr_offset_attention_scratch_bytes", "pcr_pointnet_scratch_bytes", "pcr_shutdown"] + \
+            "pcr_offset_attention_scratch_bytes", "pcr_pointnet_scratch_bytes", "pcr_edge_conv_scratch_bytes",
+            "pcr_group_mlp_scratch_bytes", "pcr_shutdown"] + \
         list(SIGNATURES)
 
 

@@ -28,6 +28,11 @@ arbitrarily and ranks by the expanded form, so it is the neighbour *set* (all
 that ``GCN``'s max over the k axis sees) that equals the reference's, not
 always the order.  ``graph_features`` is the gather ``[f_i, f_j - f_i]``, exact.
 
+What consumes ``local_ppf_features`` and ``knn_graph`` -- the Conv2d / norm /
+activation / max chains of ``LocalFeatureFused`` and ``GCN`` -- is fused in
+``groupmlp`` (``group_mlp``, ``edge_conv``): with it neither ``graph_features``'
+``(B, N, k, 2C)`` tensor nor a ``(B, C, K, N)`` activation is needed.
+
 Like ``nndistance``, the module raises on CPU tensors (there is no fallback).
 The ops are forward-only: an input that requires grad while grad mode is on
 raises instead of silently cutting the graph.
