@@ -5,10 +5,13 @@
 //   featnn_row8  S <= 2: two column tiles per step; 3-term (the fallback of the
 //                1-term screens, and the whole screen with PCR_FEAT_ONE=0) or
 //                1-term (PCR_FEAT_ROW9=0); featnn_slicemerge for its column slices;
-//   featnn_row9  S <= 2, the default 1-term sweep, with featnn_regroup9 and
-//                featnn_finish9.
+//   featnn_row9  S <= 2, the default 1-term sweep -- rows stationary (row9_rows)
+//                or columns stationary (row9_cols, the default) -- with
+//                featnn_regroup9 and featnn_finish9.
 #include "featnn_v5.h"
+#include "row9_merge.h"
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 
 namespace pcr {
@@ -784,9 +787,45 @@ __device__ __forceinline__ unsigned group_min32(const f32x16 &x, const f32x16 &y
     return umin2(umin2(c0, c1), c2);
 }
 
-// kIdx: pass 1 / pass 2 (the same code; two names for the profiles)
+// What follows a sweep, either form, for one row (lane half h of row slot k
+// holds its half's B1, B2, I): the row's two lane halves -- the smaller B1 wins
+// (the lower half on a tie: a zero gap, uncertified either way), the second
+// smallest of the union.  The row goes to its winning step's bucket as (row,
+// B1, B2, half); a row that one_term_fails, or past a full bucket, goes to the
+// 3-term screen's list instead (and its record is marked for featnn_finish9
+// to skip)
+template <int S, bool kIdx>
+__device__ __forceinline__ void row9_settle(const RowArgs5 &a, int p, const int *rl, int nr, int k, int h,
+                                            unsigned B1, unsigned B2, unsigned I) {
+    const int nst = a.ntc >> 1;
+    const unsigned o1 = (unsigned)__shfl_xor((int)B1, 32, 64);
+    const unsigned o2 = (unsigned)__shfl_xor((int)B2, 32, 64);
+    const unsigned oi = (unsigned)__shfl_xor((int)I, 32, 64);
+    const unsigned s2 = umin2(umax2(B1, o1), umin2(B2, o2));
+    const bool mine = B1 < o1 || (B1 == o1 && h == 0);
+    const unsigned w1 = mine ? B1 : o1;
+    const unsigned wst = min(mine ? I : oi, (unsigned)(nst - 1));
+    if (h == 0 && k < nr) {
+        // re-read, not kept from the operand build across the sweep (registers)
+        const int row = rl ? reinterpret_cast<const volatile int *>(rl)[k] : k;
+        const size_t bk = (size_t)p * nst + wst;
+        const bool early = one_term_fails<kIdx, S>(a, p, row, w1, s2, a.rre[(size_t)p * a.ntr * 32 + row],
+                                                   a.rct[(size_t)p * a.ntr * 32 + row]);
+        const int rank = early ? a.bcap : atomicAdd(a.bcnt + bk, 1);
+        if (rank < a.bcap) {
+            a.blist[bk * a.bcap + rank] = make_uint4((unsigned)row, w1, s2, mine ? 0u : 1u);
+        } else {
+            // (a zero counter, B1 and no column yet: featnn_thresh9's inputs)
+            a.rec[(size_t)p * a.Rmax + row] = make_uint4(0u, w1, 0xffffffffu, 1u);
+            a.list[(size_t)p * a.Rmax + atomicAdd(a.count + p, 1)] = row;
+        }
+    }
+}
+
+// The sweep, rows stationary: a wave keeps RT = 2 row tiles in registers and the
+// block streams the column groups through LDS.
 template <int S, int G, bool kIdx>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void featnn_row9(RowArgs5 a) {
+__device__ __forceinline__ void row9_rows(const RowArgs5 &a) {
     constexpr int W = 8, RT = 2;          // waves per workgroup, row tiles per wave
     constexpr int NB = S;                 // executed chunks: the f16 segment (a tile's first NB of a.ich stored)
     constexpr int kT = G * NB * 64;       // f16x8 of a B buffer's fragments
@@ -970,38 +1009,173 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void f
     }
 #pragma unroll
     for (int t = 0; t < RT; ++t) close(acc[t][1], t, pend);
-    // the row's two lane halves: the smaller B1 wins (the lower half on a tie:
-    // a zero gap, uncertified either way); the second smallest of the union.
-    // The row goes to its winning step's bucket as (row, B1, B2, half); a row
-    // that one_term_fails, or past a full bucket, goes to the 3-term screen's
-    // list instead (and its record is marked for featnn_finish9 to skip)
-    const int nst = a.ntc >> 1;
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+        row9_settle<S, kIdx>(a, p, rl, nr, (qt0 + t) * 32 + (l & 31), h, B1[t], B2[t], I[t]);
+}
+
+// The sweep, columns stationary (S <= 2): the loop above turned inside out.  A
+// workgroup still owns 16 row tiles of one pair, but its W waves split the
+// column steps (wave w takes steps w, w + W, ...) and every wave runs over all
+// 16 row tiles:
+//   - the block's row operands sit in LDS as [row tile][chunk][lane] (32 KB at
+//     S = 2, built once; a wave reads a row tile's with S ds_read_b128, one
+//     row tile ahead);
+//   - a step's column fragments go from the packed image straight to registers
+//     (each is read by one wave of the block: no LDS copy), its two tiles'
+//     terms as one float per lane and 16 DPP row broadcasts each -- once per
+//     step, shared by the 16 row tiles, where the rows-stationary loop redoes
+//     them for every pair of row tiles; the next step's are loaded meanwhile;
+//   - per row tile the identical MFMA chains, one group_min32 over both
+//     column tiles (no pm) and the close; the accumulators alternate between
+//     two sets, so a row tile's minima issue under the next one's MFMAs.
+// No barrier and no LDS write inside the loop.  The waves' triples merge
+// through LDS at the end (row9_merge.h: bit-identical to one wave taking every
+// step in order), W row tiles per round, and wave w settles row tiles
+// [w NT / W, (w + 1) NT / W) as the loop above does.
+// Registers: Cf 32, Bf 16 + 18 (the next step's), B1 / B2 / I 48, acc 64,
+// A 16: two waves per SIMD.
+template <int S, int G, bool kIdx, int W>
+__device__ __forceinline__ void row9_cols(const RowArgs5 &a) {
+    constexpr int NT = 16, RT = NT / W;   // row tiles per workgroup; settled per wave
+    constexpr int NB = S;
+    constexpr int kOp = NT * NB * 64;     // f16x8 of the row operands
+    constexpr int kMg = W * W * 3 * 16;   // f16x8 of a merge round: [wave][row tile of the round][B1, B2, I][lane]
+    static_assert(G % 2 == 0 && NT % W == 0 && S <= 2, "column tiles in pairs; whole row tiles per wave");
+    __shared__ __attribute__((aligned(16))) f16x8 As[kOp > kMg ? kOp : kMg];
+    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
+    const int ppx = (a.P + 7) >> 3;
+    const int p = a.rbmajor ? (slot % ppx) * 8 + xcd : (slot / a.nrb) * 8 + xcd;
+    const int rb = a.rbmajor ? slot / ppx : slot - (slot / a.nrb) * a.nrb;
+    if (p >= a.P) return;  // whole block
+    const int *rl = a.rlist ? a.rlist + (size_t)p * a.Rmax : nullptr;
+    const int nr = rl ? a.rcount[p] : count_of(a.n_rows, p, a.Rmax);
+    if (rb * NT * 32 >= nr) return;  // whole block: no rows here
+    // (uniform: the step loop's control stays scalar)
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63, h = l >> 5;
+    const int m = count_of(a.n_cols, p, a.Cmax);
+    const int ntc = (m + 31) >> 5;
+    const int nsteps = (ntc + G - 1) / G * (G / 2);  // the rows-stationary loop's, padding tiles included
+    f16x8 *Asl = As + l;
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
-        const unsigned o1 = (unsigned)__shfl_xor((int)B1[t], 32, 64);
-        const unsigned o2 = (unsigned)__shfl_xor((int)B2[t], 32, 64);
-        const unsigned oi = (unsigned)__shfl_xor((int)I[t], 32, 64);
-        const unsigned s2 = umin2(umax2(B1[t], o1), umin2(B2[t], o2));
-        const bool mine = B1[t] < o1 || (B1[t] == o1 && h == 0);
-        const unsigned w1 = mine ? B1[t] : o1;
-        const unsigned wst = min(mine ? I[t] : oi, (unsigned)(nst - 1));
-        const int k = (qt0 + t) * 32 + (l & 31);
-        if (h == 0 && k < nr) {
-            // re-read, not kept from the operand build across the sweep (registers)
-            const int row = rl ? reinterpret_cast<const volatile int *>(rl)[k] : k;
-            const size_t bk = (size_t)p * nst + wst;
-            const bool early = one_term_fails<kIdx, S>(a, p, row, w1, s2, a.rre[(size_t)p * a.ntr * 32 + row],
-                                                       a.rct[(size_t)p * a.ntr * 32 + row]);
-            const int rank = early ? a.bcap : atomicAdd(a.bcnt + bk, 1);
-            if (rank < a.bcap) {
-                a.blist[bk * a.bcap + rank] = make_uint4((unsigned)row, w1, s2, mine ? 0u : 1u);
-            } else {
-                // (a zero counter, B1 and no column yet: featnn_thresh9's inputs)
-                a.rec[(size_t)p * a.Rmax + row] = make_uint4(0u, w1, 0xffffffffu, 1u);
-                a.list[(size_t)p * a.Rmax + atomicAdd(a.count + p, 1)] = row;
+        const int tt = wid * RT + t;
+        const int k = (rb * NT + tt) * 32 + (l & 31);
+        f16x8 A[NB];
+        row_operand<S, kIdx ? 0 : 1>(a, p, rl ? (k < nr ? rl[k] : 0) : (k < nr ? k : 0), k < nr, h, A);
+#pragma unroll
+        for (int c = 0; c < NB; ++c) Asl[(tt * NB + c) * 64] = A[c];
+    }
+    __syncthreads();
+    unsigned B1[NT], B2[NT], I[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) { B1[t] = kRow9Inf; B2[t] = kRow9Inf; I[t] = 0u; }
+    const int nm = a.ich;  // the image's tile stride in chunks
+    const f16x8 *bsrc = a.Bp + (size_t)p * a.ntc * nm * 64 + l;
+    // lane l's column of a tile's terms (the DPP row broadcast of row position
+    // r then gives every lane its register r's column, as in the loop above)
+    const int *csrc = reinterpret_cast<const int *>(a.cct + (size_t)p * a.ntc * 32) + 8 * ((l & 15) >> 2) + (l & 3) + 4 * h;
+    auto load = [&](int st, f16x8 (&Bf)[2][NB], int (&cv)[2]) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+#pragma unroll
+            for (int c = 0; c < NB; ++c) Bf[u][c] = bsrc[((size_t)(2 * st + u) * nm + c) * 64];
+            cv[u] = csrc[(2 * st + u) * 32];
+        }
+    };
+    auto cterms = [](f32x16 &c, int v) {
+#define PCR_BC(r) c[r] = __int_as_float(__builtin_amdgcn_mov_dpp(v, 0x150 + (r), 0xf, 0xf, false))
+        PCR_BC(0); PCR_BC(1); PCR_BC(2); PCR_BC(3); PCR_BC(4); PCR_BC(5); PCR_BC(6); PCR_BC(7);
+        PCR_BC(8); PCR_BC(9); PCR_BC(10); PCR_BC(11); PCR_BC(12); PCR_BC(13); PCR_BC(14); PCR_BC(15);
+#undef PCR_BC
+    };
+    f16x8 Bf[2][NB], Ar[2][NB];
+    int cv[2];
+    f32x16 acc[2][2];  // [row tile parity][column tile of the step]
+    if (wid < nsteps) {
+        load(wid, Bf, cv);
+#pragma unroll
+        for (int c = 0; c < NB; ++c) Ar[0][c] = Asl[c * 64];
+    }
+    for (int st = wid; st < nsteps; st += W) {
+        f32x16 Cf[2];
+        cterms(Cf[0], cv[0]);
+        cterms(Cf[1], cv[1]);
+        f16x8 Bn[2][NB];
+        int cn[2];
+        load(st + W < nsteps ? st + W : st, Bn, cn);  // (the last step: its own again)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int cur = t & 1;
+#pragma unroll
+            for (int c = 0; c < NB; ++c)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    acc[cur][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bf[u][c], Ar[cur][c],
+                                                                         c == 0 ? Cf[u] : acc[cur][u], 0, 0, 0);
+#pragma unroll
+            for (int c = 0; c < NB; ++c) Ar[cur ^ 1][c] = Asl[(((t + 1) % NT) * NB + c) * 64];
+            if (t > 0)
+                row9_close(B1[t - 1], B2[t - 1], I[t - 1], group_min32(acc[cur ^ 1][0], acc[cur ^ 1][1]), (unsigned)st);
+            // 2 NB MFMAs beside the row tile before's 20 VALU; the next row
+            // tile's operand behind the first MFMA (its registers are free then)
+            SGB(0x008, 1, 0);
+            SGB(0x100, NB, 0);
+#pragma unroll
+            for (int i = 1; i < 2 * NB; ++i) {
+                SGB(0x002, 20 / (2 * NB), 0);
+                SGB(0x008, 1, 0);
             }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // the step's last row tile closes here, not under the next step's first
+        // MFMAs: carried round the loop, the compiler moved its 32 accumulators
+        // out of the terms' registers behind a wait for the last MFMA
+        row9_close(B1[NT - 1], B2[NT - 1], I[NT - 1], group_min32(acc[1][0], acc[1][1]), (unsigned)st);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+#pragma unroll
+            for (int c = 0; c < NB; ++c) Bf[u][c] = Bn[u][c];
+            cv[u] = cn[u];
         }
     }
+    // the waves' triples of a row tile and lane merged, W row tiles per round:
+    // round r takes row tiles RT j + r (j = 0 .. W - 1), wave j merges row tile
+    // RT j + r over the waves in order
+    unsigned *mg = reinterpret_cast<unsigned *>(As) + l;
+    unsigned M1[RT], M2[RT], MI[RT];
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        __syncthreads();  // every wave is past its operand reads (r = 0) / the round before's reads
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            unsigned *q = mg + (wid * W + j) * 3 * 64;
+            q[0] = B1[RT * j + r];
+            q[64] = B2[RT * j + r];
+            q[128] = I[RT * j + r];
+        }
+        __syncthreads();
+        M1[r] = kRow9Inf; M2[r] = kRow9Inf; MI[r] = 0u;
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const unsigned *q = mg + (w * W + wid) * 3 * 64;
+            row9_merge(M1[r], M2[r], MI[r], q[0], q[64], q[128]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+        row9_settle<S, kIdx>(a, p, rl, nr, (rb * NT + wid * RT + r) * 32 + (l & 31), h, M1[r], M2[r], MI[r]);
+}
+
+// kIdx: pass 1 / pass 2 (the same code; two names for the profiles).  kForm: 0
+// rows stationary, 1 / 2 columns stationary with 4 / 8 waves (two 256-thread
+// blocks or one 512-thread block per CU: two waves per SIMD either way)
+template <int S, int G, int kForm, bool kIdx>
+__global__ __launch_bounds__(kForm == 1 ? 256 : 512) __attribute__((amdgpu_waves_per_eu(kForm ? 2 : 4)))
+void featnn_row9(RowArgs5 a) {
+    if constexpr (kForm == 0) row9_rows<S, G, kIdx>(a);
+    else row9_cols<S, G, kIdx, kForm == 1 ? 4 : 8>(a);
 }
 
 // featnn_row9's second half (one launch per pass).  A pair's tiles: each
@@ -1231,6 +1405,18 @@ int launch_row8(const RowArgs5 &r0, int S, hipStream_t s) {
     return PCR_OK;
 }
 
+// The sweep's form per pass (kIdx / !kIdx): 0 rows stationary, 1 / 2 columns
+// stationary with 4 / 8 waves.  Chosen per pass by measurement (DESIGN.md
+// Round 12), as KL is: C4, featnn_bench alone, pass 1 1.06 / 0.93 / 1.13 ms and
+// pass 2 0.54 / 0.47 / 0.57 ms for forms 0 / 1 / 2
+#ifndef PCR_ROW9_FORM1
+#define PCR_ROW9_FORM1 1
+#endif
+#ifndef PCR_ROW9_FORM2
+#define PCR_ROW9_FORM2 1
+#endif
+constexpr int kRow9Form1 = PCR_ROW9_FORM1, kRow9Form2 = PCR_ROW9_FORM2;
+
 template <bool kIdx>
 int launch_row9(const RowArgs5 &r0, int S, hipStream_t s) {
     RowArgs5 r = r0;
@@ -1239,8 +1425,24 @@ int launch_row9(const RowArgs5 &r0, int S, hipStream_t s) {
     const long long nblk = 8LL * r.nrb * cdiv(r.P, 8);  // XCD-aware 1-D grid
     PCR_REQUIRE(nblk < (1LL << 31), PCR_ERR_ARG, "feature_corres: grid too large");
     constexpr int G = kIdx ? kRow9G1 : kRow9G;
-    if (S == 1) hipLaunchKernelGGL((featnn_row9<1, G, kIdx>), dim3((unsigned)nblk), dim3(512), 0, s, r);
-    else hipLaunchKernelGGL((featnn_row9<2, G, kIdx>), dim3((unsigned)nblk), dim3(512), 0, s, r);
+    // PCR_ROW9_SWEEP=rows|cols|cols8: the sweep's form (an A/B and parity
+    // switch, read on every call); unset: the default of the pass
+    int form = kIdx ? kRow9Form1 : kRow9Form2;
+    if (const char *e = getenv("PCR_ROW9_SWEEP")) {
+        if (!strcmp(e, "rows")) form = 0;
+        else if (!strcmp(e, "cols")) form = 1;
+        else if (!strcmp(e, "cols8")) form = 2;
+    }
+    const dim3 grid((unsigned)nblk);
+#define PCR_ROW9_LAUNCH(S_)                                                                                     \
+    do {                                                                                                        \
+        if (form == 0) hipLaunchKernelGGL((featnn_row9<S_, G, 0, kIdx>), grid, dim3(512), 0, s, r);             \
+        else if (form == 1) hipLaunchKernelGGL((featnn_row9<S_, G, 1, kIdx>), grid, dim3(256), 0, s, r);        \
+        else hipLaunchKernelGGL((featnn_row9<S_, G, 2, kIdx>), grid, dim3(512), 0, s, r);                       \
+    } while (0)
+    if (S == 1) PCR_ROW9_LAUNCH(1);
+    else PCR_ROW9_LAUNCH(2);
+#undef PCR_ROW9_LAUNCH
     PCR_LAUNCH_CHECK();
     return PCR_OK;
 }
