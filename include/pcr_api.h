@@ -262,8 +262,11 @@ int pcr_icp_batch(const float *src_xyz, const float *tgt_xyz, int32_t P, int32_t
  * Every buffer is device memory owned by the caller (inlier_mask optional).
  * records (P, 40) f64: [0,16) T_ransac, [16,32) T_icp, 32/33 RANSAC fitness /
  * rmse, 34/35 ICP fitness / rmse, 36 Chamfer = mean(d1) + mean(d2) (f64 sums
- * of the f32 distances in index order), 37 RANSAC iterations, 38 RANSAC
- * status, 39 correspondences after the mutual filter.
+ * of the f32 distances in one fixed order: 1024 partial sums, partial t over
+ * the indices t, t + 1024, ... in increasing order; each run of 64 partials
+ * folded by a halving tree, p[l] += p[l + h] for h = 32 ... 1; the 16 results
+ * added in order from 0.0; then sum1 / N + sum2 / M), 37 RANSAC iterations,
+ * 38 RANSAC status, 39 correspondences after the mutual filter.
  * pcr_pipeline_records: the records alone, from buffers the stage calls filled.
  * Streams: the step forks once -- RANSAC's / ICP's target grids and the source
  * spatial order are built on a library-owned side stream of the calling

@@ -81,6 +81,8 @@ def _setup_sigs():
     L.oracle_radius_thr.restype = c.c_double
     L.oracle_radius_thr.argtypes = [c.c_double]
     L.oracle_procrustes_batch.argtypes = [c.c_void_p] * 3 + [c.c_int, c.c_int, c.c_int, c.c_double, c.c_void_p]
+    L.oracle_procrustes.restype = None
+    L.oracle_procrustes.argtypes = [c.c_void_p] * 3 + [c.c_int, c.c_int, c.c_double, c.c_void_p]
     L.oracle_ransac.restype = c.c_int
     L.oracle_ransac.argtypes = ([c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.c_void_p, c.c_int,
                                  c.c_double, c.c_int, c.c_double, c.c_double, c.c_int, c.c_double,
@@ -189,6 +191,19 @@ def procrustes_batch(src, tgt, w, absw, eps):
     b, n = src.shape[0], src.shape[1]
     T = np.zeros((b, 3, 4), np.float64)
     L().oracle_procrustes_batch(_p(src), _p(tgt), _p(w), b, n, int(absw), float(eps), _p(T))
+    return T
+
+
+def procrustes_f64(src, tgt, w, absw, eps):
+    """procrustes_batch on f64 inputs as given (no rounding to f32): one
+    oracle_procrustes call per item, (B,N,3),(B,N,3),(B,N) -> T (B,3,4) f64."""
+    src, tgt, w = _f64(src), _f64(tgt), _f64(w)
+    b, n = src.shape[0], src.shape[1]
+    T = np.zeros((b, 3, 4), np.float64)
+    for p in range(b):
+        s, t, ww, Tp = src[p].copy(), tgt[p].copy(), w[p].copy(), np.zeros(12, np.float64)
+        L().oracle_procrustes(_p(s), _p(t), _p(ww), n, int(absw), float(eps), _p(Tp))
+        T[p] = Tp.reshape(3, 4)
     return T
 
 

@@ -87,7 +87,9 @@ static int procrustes_launch(const Scalar *src, const Scalar *tgt, const Scalar 
     clear_error();
     PCR_REQUIRE(B >= 0 && N >= 0, PCR_ERR_ARG, "procrustes: negative size");
     if (B == 0) return PCR_OK;
-    PCR_REQUIRE(src && tgt && weights && T, PCR_ERR_ARG, "procrustes: null pointer");
+    // N == 0: the kernel reads no input (every item comes out [I | 0]), and the
+    // pointers of empty arrays may be null
+    PCR_REQUIRE(T && (N == 0 || (src && tgt && weights)), PCR_ERR_ARG, "procrustes: null pointer");
     hipLaunchKernelGGL(procrustes_kernel<Scalar>, dim3(B), dim3(256), 0, as_stream(stream), src,
                        tgt, weights, N, abs_weights, eps, T);
     PCR_LAUNCH_CHECK();
@@ -111,7 +113,8 @@ extern "C" int pcr_procrustes_batch_f64(const double *src, const double *tgt, co
 // apply per-item rigid transforms: out = (float)(R p + t) in f64, T (B,16)
 // row-major 4x4 (the registration outputs).  The pipeline's "transform" stage
 // (aligned source for the Chamfer quality check) -- one fused pass instead of a
-// f64 batched GEMM plus casts.  float4 loads/stores over the flat (B*N*3) array.
+// f64 batched GEMM plus casts.  One thread per point: three scalar f32 loads,
+// three scalar f32 stores; the fourth row of T is not read.
 // ---------------------------------------------------------------------------
 namespace pcr {
 namespace {
