@@ -1199,6 +1199,89 @@ int pcr_group_mlp(const float *x, int32_t b, int32_t n, int32_t K, int32_t cin, 
                   int32_t group, double eps, float slope, int32_t channels_first, float *out, void *scratch,
                   pcr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * The unary family of NgeNet's KPConv blocks and decoder, fused for inference
+ * (c2p-net/ngenet/models/KPConv/blocks.py:135-290, NgeNet.py:185-212): rows
+ * times a weight, the norm over the whole stacked cloud, the residual add and
+ * the LeakyReLU.  UnaryBlock, BatchNormBlock, the residual add of
+ * ResnetBottleneckBlock and NearestUpsampleBlock + torch.cat + UnaryBlock are
+ * each ONE call; the up-sampled rows and the concatenated operand are never in
+ * global memory.  The f64 restatement with the derived bounds is
+ * tests/unary_ref.py.
+ *
+ * pcr_unary_forward: for row i < n and output channel o < cout
+ *     row_i     = [ x0[g0 ? g0[i] : i][0 .. c0) | x1[i][0 .. c1) ]
+ *     y[i][o]   = sum_c w[o][c] row_i[c]          (w null: y[i][o] = row_i[o])
+ *     pre[i][o] = norm ? fmaf(y, a[o], b[o]) : y + bias[o]   (bias null: y)
+ *     z         = res ? pre + res[i][o] : pre
+ *     out[i][o] = act ? (z > 0 ? z : slope z) : z
+ *   the norm an InstanceNorm1d without affine over the n rows (biased variance).
+ *
+ * How it is computed (what the contract fixes).
+ *   Product.  f32 in, f32 accumulate, on v_mfma_f32_32x32x2_f32, the exact-f32
+ *     MFMA: per element one chain over the c0 + c1 inputs ascending from +0
+ *     (k-step t adds inputs 2 t, then 2 t + 1; the concat seam may fall inside
+ *     a k-step).  The gather and the concat happen while a 64-row tile is
+ *     staged into LDS, 32 inputs at a time; inputs past c0 + c1, channels past
+ *     cout and rows past n are staged as +0.  A g0[i] outside [0, m0) reads a
+ *     row of zeros (KPConv's shadow row; the reference would raise).  Every
+ *     access stays in range for any index value.
+ *   Statistics.  Per channel sum y and sum y^2 are f64 sums of the f32 y (the
+ *     square formed in f64, exact): rows in ascending order within a tile of 64
+ *     rows; the tiles' partials are added in 16 runs of ceil(tiles / 16)
+ *     consecutive tiles, each in ascending tile order, and the runs' sums in
+ *     run order (the finalize kernel pcr_group_mlp uses).  mean = S / n,
+ *     var = S2 / n - mean^2 (clamped at 0), rstd = 1 / sqrt(var + eps), all
+ *     f64; a = rstd and b = -mean rstd are each rounded ONCE to f32.  No
+ *     atomics.  Tile t is rows 64 t .. 64 t + 63: the map depends on n only,
+ *     never on the grid.
+ *   Apply.  pre = fmaf(y, a, b) with norm, else y + bias (one f32 add);
+ *     z = pre + res (one f32 add); out = z > 0 ? z : slope z (one f32 product).
+ *   Passes.  (1) product tile -> the raw y written to out, and the tile's
+ *     partials; (2) finalize; (3) apply in place over out.  With norm = 0
+ *     pass 1 alone writes the final value.  Pass 3 reads out back: it does not
+ *     recompute the product, because the blocks' input is wider than their
+ *     output (DESIGN.md "Unary blocks").  w null: (1') statistics of the rows
+ *     themselves, (2), and (3) reading the rows where they are.
+ *   Consequences: two calls return the same bytes; the bytes do not depend on
+ *     the launch grid; y and stats of a call equal those of the same call
+ *     without res and act; out of a call without norm, res and act equals
+ *     y + bias bit for bit.
+ * Layout.  x0 (m0, c0) and x1 (n, c1) with row strides ld0, ld1 in elements
+ *   (>= c0, c1); g0 (n) int32; w (cout, c0 + c1) row-major (nn.Linear's);
+ *   bias (cout); res, out and y (n, cout) contiguous; stats (cout, 2) f64
+ *   (mean, var), only with norm.  out may not overlap an input except res.
+ * Non-finite inputs: unspecified values; every access stays in range and every
+ *   kernel terminates.
+ * Limits.  n in 0 .. 2^22 (n >= 2 with norm: torch's InstanceNorm1d refuses one
+ *   spatial element), m0 >= 1, c0 >= 1, c1 >= 0, c0 + c1 <= 2048, cout in
+ *   1 .. 1024, eps >= 0, |slope| <= 1.  bias together with norm, stats without
+ *   norm, w null with cout != c0 + c1, g0 null with m0 != n, x1 null with
+ *   c1 != 0, or a null required pointer (args, x0, out, scratch) returns
+ *   PCR_ERR_ARG with its message before any device work; n = 0 returns PCR_OK
+ *   without a launch.
+ * Scratch (16-byte aligned): a | b (2 cout floats) and the per-tile partials
+ *   (2 ceil(n / 64) cout doubles).  pcr_unary_scratch_bytes returns -1 on bad
+ *   sizes, the text in pcr_last_error.
+ * The call is asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+typedef struct pcr_unary_args {          /* a HOST struct of device pointers */
+    int32_t n, m0, c0, c1, cout;
+    const float *x0; int64_t ld0;        /* (m0, c0), row stride in elements */
+    const int32_t *g0;                   /* (n) or null: row i reads x0[g0[i]], else x0[i] (then m0 == n) */
+    const float *x1; int64_t ld1;        /* (n, c1) or null with c1 = 0 */
+    const float *w;                      /* (cout, c0 + c1) row-major, or null: y = the row itself */
+    const float *bias;                   /* (cout) or null; only with norm = 0 */
+    int32_t norm; double eps;            /* InstanceNorm over the n rows, biased variance */
+    int32_t act; float slope;            /* LeakyReLU, applied last */
+    const float *res;                    /* (n, cout) contiguous or null */
+    float *out;                          /* (n, cout) contiguous */
+    float *y; double *stats;             /* optional: raw pre-norm y, (cout, 2) f64 mean / var */
+} pcr_unary_args;
+
+int64_t pcr_unary_scratch_bytes(int32_t n, int32_t cout);
+int pcr_unary_forward(const pcr_unary_args *a, void *scratch, pcr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,15 +23,19 @@ reference's operator interfaces:
                  conv of NgeNet's GCN and the grouped local-feature MLP of
                  NgeNet's PPF and ROPNet's LocalFeatue, fused (no per-neighbour
                  activation), with GCN / PPF / LocalFeature modules and fuse()
+  ngenet         the unary family of NgeNet's KPConv blocks and decoder (rows
+                 times weight, whole-cloud InstanceNorm, residual, LeakyReLU;
+                 the decoder's up-sampling and concat inside the kernel), the
+                 block modules and fuse(), and forward(): NgeNet end to end
 """
 from ._lib import PcrError, load as load_library  # noqa: F401
 
-__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd", "attention", "pointnet", "groupmlp"]
+__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd", "attention", "pointnet", "groupmlp", "ngenet"]
 
 
 def __getattr__(name):
     # the op modules import torch; the package itself (ABI loader) does not
-    if name in ("grouping", "matching", "cpd", "attention", "pointnet", "groupmlp"):
+    if name in ("grouping", "matching", "cpd", "attention", "pointnet", "groupmlp", "ngenet"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -64,6 +64,13 @@ class GroupMlpNet(ctypes.Structure):
                 ("y", _p * 3), ("stats", _p * 3)]
 
 
+class UnaryArgs(ctypes.Structure):
+    """pcr_unary_args (include/pcr_api.h): a host struct of device pointers."""
+    _fields_ = [("n", _i32), ("m0", _i32), ("c0", _i32), ("c1", _i32), ("cout", _i32), ("x0", _p), ("ld0", _i64),
+                ("g0", _p), ("x1", _p), ("ld1", _i64), ("w", _p), ("bias", _p), ("norm", _i32), ("eps", _f64),
+                ("act", _i32), ("slope", _f32), ("res", _p), ("out", _p), ("y", _p), ("stats", _p)]
+
+
 _rp = ctypes.POINTER(RansacParams)
 _ip = ctypes.POINTER(IcpParams)
 
@@ -137,6 +144,7 @@ SIGNATURES = {
     "pcr_edge_conv": [_p, _i64, _i64, _i64, _p, _i32, _i32, _i32, _i32, _i32, _p, _f64, _f32, _i32, _p, _p, _p, _p,
                       _p],
     "pcr_group_mlp": [_p, _i32, _i32, _i32, _i32, ctypes.POINTER(GroupMlpNet), _i32, _f64, _f32, _i32, _p, _p, _p],
+    "pcr_unary_forward": [ctypes.POINTER(UnaryArgs), _p, _p],
 }
 
 
@@ -196,6 +204,8 @@ def load():
         lib.pcr_edge_conv_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32]
         lib.pcr_group_mlp_scratch_bytes.restype = _i64
         lib.pcr_group_mlp_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, _i32]
+        lib.pcr_unary_scratch_bytes.restype = _i64
+        lib.pcr_unary_scratch_bytes.argtypes = [_i32, _i32]
         lib.pcr_shutdown.restype = ctypes.c_int
         lib.pcr_shutdown.argtypes = []
         for name, args in SIGNATURES.items():
@@ -216,7 +226,7 @@ def exported_symbols():
             "pcr_ndp_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words", "pcr_ndp_chamfer_max_points",
             "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_attention_scratch_bytes",
             "pcr_offset_attention_scratch_bytes", "pcr_pointnet_scratch_bytes", "pcr_edge_conv_scratch_bytes",
-            "pcr_group_mlp_scratch_bytes", "pcr_shutdown"] + \
+            "pcr_group_mlp_scratch_bytes", "pcr_unary_scratch_bytes", "pcr_shutdown"] + \
         list(SIGNATURES)
 
 

@@ -6,6 +6,9 @@ RANSAC and the NDP non-rigid refinement, with the reference's names.
   execute_global_registration  c2p-net/ngenet/utils/o3d.py:164-184
   register_c2p                 c2p-net/testScript.py:161-196 (vote -> global
                                registration -> NDP on the unique inlier sources)
+  describe                     c2p-net/testScript.py:136-159 (the network's forward,
+                               ngenet.forward, split into the per-cloud h / m / l
+                               features register_c2p takes)
 
 The three nearest-target searches of vote run as one batched feature screen
 (pcr_feature_match, P = 3 levels when they share a shape) and the distance tests
@@ -150,5 +153,17 @@ def register_c2p(source, target, source_feats, target_feats, voxel_size, dist_th
             "source_feats_h": fs_h, "target_feats_h": ft_h}
 
 
-__all__ = ["get_coor_points", "vote", "execute_global_registration", "register_c2p", "Feature",
+def describe(model, inputs):
+    """testScript.py:136-159: run a loaded NgeNet on libpcr (ngenet.forward) and split its three
+    outputs at the source cloud's length.  Returns (source_feats, target_feats), each the list
+    [h, m, l] of device tensors register_c2p and vote take: h without its two score columns."""
+    from . import ngenet
+    with torch.no_grad():
+        feats_h, feats_m, feats_l = ngenet.forward(model, inputs)
+    n_src = int(inputs["stacked_lengths"][0][0])
+    levels = (feats_h[:, :-2], feats_m, feats_l)
+    return [f[:n_src] for f in levels], [f[n_src:] for f in levels]
+
+
+__all__ = ["get_coor_points", "vote", "execute_global_registration", "register_c2p", "describe", "Feature",
            "PointCloud"]

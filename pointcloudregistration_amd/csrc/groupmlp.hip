@@ -28,7 +28,8 @@
 //                 squares to the tile's partial, max / min per group to scratch.
 //  edge_gemm      R = P - Q and Q for 64 points and 128 channels per workgroup.
 //  edge_reduce    per point and channel the kk neighbours in order.
-//  norm_finalize  per (cloud, channel): the partials in 16 runs of consecutive tiles,
+//  norm_finalize  (norm_finalize.h, shared with unary.hip) per (cloud, channel):
+//                 the partials in 16 runs of consecutive tiles,
 //                 each in ascending order, the runs' sums in run order;
 //                 mean / var / rstd in f64, a and b rounded once.
 //  norm_output    out = act(fmaf(max or min, a, b)), either layout (the
@@ -39,6 +40,7 @@
 // SIMD, kept busy by eight independent accumulators.
 #include <math.h>
 
+#include "norm_finalize.h"
 #include "pcr_internal.h"
 #include "wave.h"
 #include "workspace.h"
@@ -46,6 +48,10 @@
 namespace {
 
 using pcr::cdiv64;
+using pcr::FinArgs;
+using pcr::kFinRuns;
+using pcr::kFinThreads;
+using pcr::norm_finalize;
 using pcr::WsLayout;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -61,9 +67,6 @@ constexpr int kMaxB = 65535;    // gridDim.y
 constexpr int kXLd = kMaxCin + 1;
 constexpr int kWaveBlk = kMaxC / 32 / 4;  // channel blocks per wave
 constexpr int kEdgePts = 8;     // points per edge_reduce workgroup: its statistics tile
-constexpr int kFinThreads = 64;
-constexpr int kFinDepth = 32;   // partials a norm_finalize lane has in flight
-constexpr int kFinRuns = 16;    // waves of a norm_finalize workgroup: runs of consecutive tiles
 
 // row of the 32x32 tile held in accumulator register r of lane half hh
 __device__ __forceinline__ int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
@@ -349,72 +352,6 @@ __global__ __launch_bounds__(kThreads) void edge_reduce(EdgeArgs a) {
         double *p = a.part + (((size_t)b * a.tiles + t) * co + c) * 2;
         p[0] = s;
         p[1] = ss;
-    }
-}
-
-struct FinArgs {
-    const double *part;  // (b, tiles, C, 2)
-    const float *gamma, *beta;  // (C) or null
-    float *coef;         // (b, C, 2)
-    double *stats;       // (b, C / g, 2): mean, var; or null
-    double count, eps;   // values per channel and cloud
-    int tiles, C, g;
-};
-
-__global__ __launch_bounds__(kFinThreads * kFinRuns) void norm_finalize(FinArgs a) {
-    __shared__ double2 runs[kFinRuns][kFinThreads];
-    const int lane = threadIdx.x & 63, c = blockIdx.x * kFinThreads + lane, b = blockIdx.y;  // C is a multiple of 32
-    const int run = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool in = c < a.C;
-    double s = 0.0, ss = 0.0;
-    if (in) {
-        // wave `run` adds its run of ceil(tiles / 16) consecutive tiles in ascending order, 32 independent
-        // loads in flight per lane (one dependent load per tile made this walk a third of the call)
-        const int len = (a.tiles + kFinRuns - 1) / kFinRuns, t1 = min(a.tiles, (run + 1) * len);
-        const double2 *p = reinterpret_cast<const double2 *>(a.part) + (size_t)b * a.tiles * a.C + c;
-        for (int t0 = run * len; t0 < t1; t0 += kFinDepth) {
-            double2 v[kFinDepth];
-#pragma unroll
-            for (int i = 0; i < kFinDepth; ++i) v[i] = p[(size_t)min(t0 + i, t1 - 1) * a.C];
-#pragma unroll
-            for (int i = 0; i < kFinDepth; ++i)
-                if (t0 + i < t1) {
-                    s += v[i].x;
-                    ss += v[i].y;
-                }
-        }
-    }
-    runs[run][lane] = make_double2(s, ss);
-    __syncthreads();
-    if (run != 0) return;
-    s = 0.0; ss = 0.0;
-    for (int r = 0; r < kFinRuns; ++r) {  // the runs' sums in run order
-        s += runs[r][lane].x;
-        ss += runs[r][lane].y;
-    }
-    double cnt = a.count;
-    if (a.g == 32) {  // the group's 32 channels sit in one lane half: summed over channels ascending
-        const int base = lane & 32;
-        double gs = 0.0, gss = 0.0;
-        for (int j = 0; j < 32; ++j) {
-            gs += __shfl(s, base + j, 64);
-            gss += __shfl(ss, base + j, 64);
-        }
-        s = gs; ss = gss; cnt *= 32.0;
-    }
-    if (!in) return;
-    const double mean = s / cnt;
-    double var = ss / cnt - mean * mean;
-    if (!(var > 0.0)) var = 0.0;
-    const double a64 = (a.gamma ? (double)a.gamma[c] : 1.0) * (1.0 / sqrt(var + a.eps));
-    const double b64 = (a.beta ? (double)a.beta[c] : 0.0) - mean * a64;
-    float *cf = a.coef + ((size_t)b * a.C + c) * 2;
-    cf[0] = (float)a64;
-    cf[1] = (float)b64;
-    if (a.stats && (a.g == 1 || (lane & 31) == 0)) {
-        double *st = a.stats + ((size_t)b * (a.C / a.g) + c / a.g) * 2;
-        st[0] = mean;
-        st[1] = var;
     }
 }
 
