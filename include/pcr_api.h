@@ -1282,6 +1282,97 @@ typedef struct pcr_unary_args {          /* a HOST struct of device pointers */
 int64_t pcr_unary_scratch_bytes(int32_t n, int32_t cout);
 int pcr_unary_forward(const pcr_unary_args *a, void *scratch, pcr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Point-wise convolutions of ROPNet (CG.py:15-106, TFMR.py:76-130), fused for
+ * inference: a Conv1d(k = 1) weight times channel-major clouds (B, C, N), the
+ * GroupNorm over (cloud, channel group, all points), the biases, the
+ * (Leaky)ReLU, the residual add BEHIND it and the max over points, as ONE
+ * call.  The operand is up to five sources side by side, each optionally
+ * minus a second tensor: torch.cat([x1 .. x5]), x - x_r and the
+ * (B, 6144, N) ensemble of the CG's overlap decoder are never in global
+ * memory.  The f64 restatement with the derived bounds is
+ * tests/pointwise_ref.py.
+ *
+ * pcr_pointwise_forward: for cloud b, output channel o < cout, point i < n
+ *     row[c]       = concat over s < nsrc of src_s[b][c][i] - (sub_s ? sub_s[b][c][i] : 0),  c < cin = sum c_s
+ *     y[b][o][i]   = sum_c w[o][c] row[c]
+ *     t            = (y + bias[o]) + cbias[b][o]        (two rounded f32 adds; null: skipped)
+ *     pre          = gw ? fmaf(t, A[b][o], Bc[b][o]) : t
+ *     z            = act ? (pre > 0 ? pre : slope pre) : pre
+ *     out[b][o][i] = res ? z + res[b][o][i] : z          (the residual after the activation, TFMR.py:104-105)
+ *     cmax[b][o]   = max_i out[b][o][i]                  (optional)
+ *   the norm a GroupNorm over gw consecutive channels (cout % gw == 0) times the
+ *   n points of one cloud, its statistics those of t (a Conv1d bias in front
+ *   of a GroupNorm shifts a group's mean), biased variance, affine gamma /
+ *   beta (null: 1, 0).
+ *
+ * How it is computed (what the contract fixes).
+ *   Product.  f32 in, f32 accumulate, on v_mfma_f32_32x32x2_f32 with w as the A
+ *     operand: per element one fmaf chain over the cin inputs ascending from +0
+ *     (k-step t adds inputs 2 t, then 2 t + 1; a seam between sources may fall
+ *     inside a k-step).  src - sub is one rounded f32 subtraction made while a
+ *     64-point tile is staged into LDS, 32 inputs at a time; inputs past cin,
+ *     channels past cout and points past n are staged as +0.  For n <= 4 the
+ *     same chain runs on the VALU (fmaf(w, x, acc), the tail padded with +0 to
+ *     the same multiple of 32): the same bytes as the tile path.
+ *   Statistics.  f64 sums of t and t^2 (the square formed in f64, exact) per
+ *     (cloud, 64-point tile, channel), points ascending; a channel's tiles are
+ *     added as pcr_unary_forward's are (16 runs, norm_finalize.h), a group's
+ *     channels ascending.  mean = S / (n gw), var = S2 / (n gw) - mean^2
+ *     (clamped at 0), A = gamma / sqrt(var + eps), Bc = beta - mean A, in f64,
+ *     each rounded ONCE to f32.  No atomics; tile t is points 64 t .. 64 t + 63.
+ *   Passes.  (1) product tile -> t written to out, and the partials;
+ *     (2) finalize; (3) apply in place over out.  With gw = 0 pass 1 alone
+ *     writes the final values.
+ *   cmax.  The maximum of each (tile, channel) from -inf, then the tiles in
+ *     order: a max is exact in any order.  No float atomics.
+ *   Consequences: two calls return the same bytes; the bytes do not depend on
+ *     the launch grid; a cloud computed alone has the bytes it has inside a
+ *     batch; sources given in pieces or minus a sub have the bytes of the
+ *     same call on the materialised torch.cat / difference.
+ * Layout.  Every source, sub, res and out has a batch stride and a channel
+ *   stride in elements (any value; 0 repeats) and point stride 1.  w (cout, cin)
+ *   row-major (nn.Conv1d's) with row stride w_ld in cin .. 8192 (a column slice
+ *   of a wider weight is read where it lies); bias, gamma, beta (cout); cbias, cmax (b, cout);
+ *   y (b, cout, n) contiguous; stats (b, cout / gw, 2) f64 (mean, var).  out may
+ *   not overlap an input except res.
+ * Non-finite inputs: unspecified values; every access stays in range and every
+ *   kernel terminates.
+ * Limits.  b in 0 .. 65535, n in 0 .. 2^22, nsrc in 1 .. 5, every c_s >= 1,
+ *   cin <= 8192, cout in 1 .. 2048, eps >= 0, |slope| <= 1.  gamma / beta /
+ *   stats without a norm, a gw that does not
+ *   divide cout, out null other than with cmax and gw = 0, or a null required
+ *   pointer returns PCR_ERR_ARG with its message before any device work; b = 0
+ *   or n = 0 returns PCR_OK without a launch.
+ * Scratch (16-byte aligned): A | Bc (2 b cout floats) and the per-tile partials
+ *   (2 b ceil(n / 64) cout doubles; the tiles' maxima take their place once they
+ *   are finalized).  Nothing is proportional to cin n.
+ *   pcr_pointwise_scratch_bytes returns -1 on bad sizes, the text in
+ *   pcr_last_error.
+ * The call is asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+#define PCR_POINTWISE_MAX_SOURCES 5
+typedef struct pcr_pointwise_args {      /* a HOST struct of device pointers */
+    int32_t b, n, nsrc, cout;
+    int32_t c[PCR_POINTWISE_MAX_SOURCES];            /* channels of source s */
+    const float *src[PCR_POINTWISE_MAX_SOURCES];
+    int64_t src_bs[PCR_POINTWISE_MAX_SOURCES], src_cs[PCR_POINTWISE_MAX_SOURCES];
+    const float *sub[PCR_POINTWISE_MAX_SOURCES];     /* null: nothing subtracted */
+    int64_t sub_bs[PCR_POINTWISE_MAX_SOURCES], sub_cs[PCR_POINTWISE_MAX_SOURCES];
+    const float *w; int64_t w_ld;        /* (cout, cin) row-major, row stride in elements */
+    const float *bias, *cbias;           /* (cout), (b, cout) or null */
+    int32_t gw; double eps;              /* GroupNorm over gw channels x n points; 0: none */
+    const float *gamma, *beta;           /* (cout) or null */
+    int32_t act; float slope;
+    const float *res; int64_t res_bs, res_cs;        /* or null */
+    float *out; int64_t out_bs, out_cs;
+    float *cmax;                         /* (b, cout) or null */
+    float *y; double *stats;             /* optional: the raw product y, (b, cout / gw, 2) f64 mean / var of t */
+} pcr_pointwise_args;
+
+int64_t pcr_pointwise_scratch_bytes(int32_t b, int32_t n, int32_t cout);
+int pcr_pointwise_forward(const pcr_pointwise_args *a, void *scratch, pcr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,15 +27,20 @@ reference's operator interfaces:
                  times weight, whole-cloud InstanceNorm, residual, LeakyReLU;
                  the decoder's up-sampling and concat inside the kernel), the
                  block modules and fuse(), and forward(): NgeNet end to end
+  ropnet         ROPNet's point-wise convolutions (Conv1d weight times (B, C, N)
+                 clouds, GroupNorm, biases, ReLU, residual and max over points
+                 as one call; concat and subtraction inside the kernel), the
+                 PointNet / CG / OverlapAttention modules and fuse(), and
+                 forward(): ROPNet end to end
 """
 from ._lib import PcrError, load as load_library  # noqa: F401
 
-__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd", "attention", "pointnet", "groupmlp", "ngenet"]
+__all__ = ["PcrError", "load_library", "grouping", "matching", "cpd", "attention", "pointnet", "groupmlp", "ngenet", "ropnet"]
 
 
 def __getattr__(name):
     # the op modules import torch; the package itself (ABI loader) does not
-    if name in ("grouping", "matching", "cpd", "attention", "pointnet", "groupmlp", "ngenet"):
+    if name in ("grouping", "matching", "cpd", "attention", "pointnet", "groupmlp", "ngenet", "ropnet"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -71,6 +71,16 @@ class UnaryArgs(ctypes.Structure):
                 ("act", _i32), ("slope", _f32), ("res", _p), ("out", _p), ("y", _p), ("stats", _p)]
 
 
+class PointwiseArgs(ctypes.Structure):
+    """pcr_pointwise_args (include/pcr_api.h): a host struct of device pointers."""
+    _fields_ = [("b", _i32), ("n", _i32), ("nsrc", _i32), ("cout", _i32), ("c", _i32 * 5), ("src", _p * 5),
+                ("src_bs", _i64 * 5), ("src_cs", _i64 * 5), ("sub", _p * 5), ("sub_bs", _i64 * 5),
+                ("sub_cs", _i64 * 5), ("w", _p), ("w_ld", _i64), ("bias", _p), ("cbias", _p), ("gw", _i32), ("eps", _f64),
+                ("gamma", _p), ("beta", _p), ("act", _i32), ("slope", _f32), ("res", _p), ("res_bs", _i64),
+                ("res_cs", _i64), ("out", _p), ("out_bs", _i64), ("out_cs", _i64), ("cmax", _p), ("y", _p),
+                ("stats", _p)]
+
+
 _rp = ctypes.POINTER(RansacParams)
 _ip = ctypes.POINTER(IcpParams)
 
@@ -145,6 +155,7 @@ SIGNATURES = {
                       _p],
     "pcr_group_mlp": [_p, _i32, _i32, _i32, _i32, ctypes.POINTER(GroupMlpNet), _i32, _f64, _f32, _i32, _p, _p, _p],
     "pcr_unary_forward": [ctypes.POINTER(UnaryArgs), _p, _p],
+    "pcr_pointwise_forward": [ctypes.POINTER(PointwiseArgs), _p, _p],
 }
 
 
@@ -206,6 +217,8 @@ def load():
         lib.pcr_group_mlp_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, _i32]
         lib.pcr_unary_scratch_bytes.restype = _i64
         lib.pcr_unary_scratch_bytes.argtypes = [_i32, _i32]
+        lib.pcr_pointwise_scratch_bytes.restype = _i64
+        lib.pcr_pointwise_scratch_bytes.argtypes = [_i32, _i32, _i32]
         lib.pcr_shutdown.restype = ctypes.c_int
         lib.pcr_shutdown.argtypes = []
         for name, args in SIGNATURES.items():
@@ -226,7 +239,8 @@ def exported_symbols():
             "pcr_ndp_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words", "pcr_ndp_chamfer_max_points",
             "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_attention_scratch_bytes",
             "pcr_offset_attention_scratch_bytes", "pcr_pointnet_scratch_bytes", "pcr_edge_conv_scratch_bytes",
-            "pcr_group_mlp_scratch_bytes", "pcr_unary_scratch_bytes", "pcr_shutdown"] + \
+            "pcr_group_mlp_scratch_bytes", "pcr_unary_scratch_bytes", "pcr_pointwise_scratch_bytes",
+            "pcr_shutdown"] + \
         list(SIGNATURES)
 
 
