@@ -358,26 +358,53 @@ int pcr_legacy_choice_batch(uint32_t *key, int32_t *pos, const int32_t *pop, int
 /* ---------------------------------------------------------------------------
  * a10 -- NDP deformation-pyramid warp, all levels in one launch.  Replaces
  * Deformation_Pyramid.warp (c2p-net/deformationpyramid/model/nets.py:36-48)
- * over NDPLayer.forward (:111-140) with motion "SE3", rotation "axis_angle"
- * (the C5 configuration, config/NDP.yaml).  Weights in nn.Linear layout
+ * over NDPLayer.forward (:111-161) for every head of the reference: motion
+ * "SE3", "Sim3" or "sflow", rotation "axis_angle", "euler", "quaternion" or
+ * "6D" (config/NDP.yaml ships SE3 / axis_angle, the C5 configuration).
+ * Weights in nn.Linear layout
  * (out, in) f32, device pointers; w_hid holds the depth-1 MLP layers
  * contiguously; w_nr/b_nr NULL for levels without the nonrigidity branch.
- * levels is a HOST array of n_levels (<= 16) entries.  x_levels (n_levels,N,3)
+ * levels is a HOST array of n_levels (<= 16) entries that share one head.
+ * x_levels (n_levels,N,3)
  * and nonrigidity (n_levels,N) are optional per-level outputs (data[i]).
  * A point's result does not depend on its position in the cloud.  NaN
- * propagates as in the reference: a point a level made NaN (a rotation branch
- * that is exactly 0 divides 0 by 0) is NaN in every later level's points and
- * nonrigidity (the ReLU keeps NaN, as torch's does).
+ * propagates as in the reference: a point a level made NaN (an axis_angle or
+ * quaternion rotation branch that is exactly 0 divides 0 by 0; an euler one
+ * gives R = I and a 6D one R = 0, both finite) is NaN in every later level's
+ * points and nonrigidity (the ReLU keeps NaN, as torch's does).
+ *
+ * Head code = rotation format + 4 * motion (PCR_NDP_HEAD): format 0 axis_angle,
+ * 1 euler, 2 quaternion, 3 6D; motion 0 SE3 (y = R x + t), 1 Sim3
+ * (y = c R x + t, c = 1e-3 (w_s h + b_s) + 1), 2 sflow (y = x + t, code 8 only,
+ * w_rot / b_rot unused).  Code 0 is SE3 / axis_angle: a zero-initialised
+ * descriptor means what it always meant.  Rows of w_rot per format: 3, 3, 4, 6.
+ * pcr_ndp_head_rows(head, what): what 0 the rows of w_rot, 1 the rows of the
+ * aux / dO scratch of pcr_ndp_train, 2 the rows of its branch-gradient buffer,
+ * 3 the first of the three translation rows, 4 the nonrigidity row, 5 the scale
+ * row, 6 the first of the three R x rows of aux (5, 6: -1 unless Sim3); -1 for
+ * an unknown head or what.
  * ------------------------------------------------------------------------- */
+#define PCR_NDP_ROT_AXIS_ANGLE 0
+#define PCR_NDP_ROT_EULER 1
+#define PCR_NDP_ROT_QUATERNION 2
+#define PCR_NDP_ROT_6D 3
+#define PCR_NDP_MOTION_SE3 0
+#define PCR_NDP_MOTION_SIM3 1
+#define PCR_NDP_MOTION_SFLOW 2
+#define PCR_NDP_HEAD(motion, rot) ((motion) == PCR_NDP_MOTION_SFLOW ? 8 : 4 * (motion) + (rot))
 typedef struct pcr_ndp_level {
     const float *w_in, *b_in;   /* (W,6), (W) */
     const float *w_hid, *b_hid; /* (depth-1,W,W), (depth-1,W) */
-    const float *w_rot, *b_rot; /* (3,W), (3) */
+    const float *w_rot, *b_rot; /* (R,W), (R), R = 3, 3, 4, 6 by format; unused for sflow */
     const float *w_trn, *b_trn; /* (3,W), (3) */
     const float *w_nr, *b_nr;   /* (1,W), (1) or NULL */
     int32_t m;                  /* level index + 1: omega = 2^(m + k0) */
     int32_t reserved;
+    const float *w_s, *b_s;     /* (1,W), (1): the Sim3 scale branch, NULL otherwise */
+    int32_t head;               /* head code, 0 = SE3 / axis_angle */
+    int32_t reserved2;
 } pcr_ndp_level;
+int32_t pcr_ndp_head_rows(int32_t head, int32_t what);
 int pcr_ndp_warp(const float *x, int32_t N, const pcr_ndp_level *levels, int32_t n_levels,
                  int32_t width, int32_t depth, int32_t k0, float *x_out, float *x_levels,
                  float *nonrigidity, pcr_stream_t stream);
@@ -556,14 +583,24 @@ int pcr_set_gate(const double *gate);
  *   level.b_hid unused: the hidden layers are w_hid[k] / b_hid[k], k < depth-1,
  *   read in place so the optimizer updates them directly); width 128.
  *   Scratch (device, feature-major [F][N]): pe [6][N], H [depth][W][N],
- *   aux [8][N], dO [8][N], D [depth][W][N]; x_out (N,3) the warped points.
+ *   aux [A][N], dO [A][N], D [depth][W][N]; x_out (N,3) the warped points.
  *   g (N,3) = dL/dx_out (e.g. the Chamfer gradient), bce_scale = w_reg / N for
  *   a level with the nonrigidity branch (BCE(s, 0) mean), else 0.
+ *   Branch rows, by level.head (one row map for aux, dO and the branch gradients):
+ *     code 0 (SE3 / axis_angle): A = 8; rot 0-2, trn 3-5, nr 6; 7 gradient rows.
+ *     codes 1-8: A = 16; rot 0-5 (the format's 3, 3, 4 or 6 rows first), trn 6-8,
+ *       nr 9, scale 10; 11 gradient rows; aux alone also holds R x of a Sim3
+ *       head in rows 11-13.
+ *     aux: r = 1e-3 o_rot in the rot rows, y (the motion's output before the
+ *     nonrigidity blend) in the trn rows, s in the nr row, c in the scale row.
+ *     dO: dL/d(branch pre-activation).  Rows a head does not use are exact
+ *     zeros in aux, dO and the branch gradients (pcr_ndp_head_rows gives the counts).
  * pcr_ndp_train_forward: x_out, and the saved activations.
  * pcr_ndp_train_backward: the gradients of every parameter of the level into
  *   grads (HOST array of device pointers): {w_in, b_in, w_hid[0], b_hid[0], ...,
- *   w_branch (7 x W rows: rot 0-2, trn 3-5, nr 6), b_branch (7)}; part is
- *   scratch of pcr_ndp_train_partial_floats(N, width, depth, chunk) floats.
+ *   w_branch (B x W rows in the head's row map, B = 7 or 11), b_branch (B)}; part is
+ *   scratch of pcr_ndp_train_partial_floats_head(N, width, depth, chunk, head)
+ *   floats (pcr_ndp_train_partial_floats: head 0).  Width 128, depth <= 5.
  * ------------------------------------------------------------------------- */
 typedef struct pcr_ndp_train {
     const float *x;
@@ -591,6 +628,8 @@ int pcr_ndp_train_forward(const pcr_ndp_train *t, pcr_stream_t stream);
 int pcr_ndp_train_backward(const pcr_ndp_train *t, float *part, int32_t chunk,
                            float *const *grads, pcr_stream_t stream);
 int64_t pcr_ndp_train_partial_floats(int32_t N, int32_t width, int32_t depth, int32_t chunk);
+int64_t pcr_ndp_train_partial_floats_head(int32_t N, int32_t width, int32_t depth, int32_t chunk,
+                                          int32_t head);
 /* pcr_ndp_chamfer_glue: the loss of registration.py:231-244 around the Chamfer
  *   pass, on the device, in a fixed reduction order:
  *   loss = sum(d1')/K + sum(d2')/M (+ w_reg * mean(-max(log(1 - s), -100)) when s

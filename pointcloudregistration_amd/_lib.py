@@ -193,6 +193,10 @@ def load():
         lib.pcr_featnn_image_chunks.argtypes = [ctypes.POINTER(_i32)]
         lib.pcr_ndp_train_partial_floats.restype = _i64
         lib.pcr_ndp_train_partial_floats.argtypes = [_i32, _i32, _i32, _i32]
+        lib.pcr_ndp_train_partial_floats_head.restype = _i64
+        lib.pcr_ndp_train_partial_floats_head.argtypes = [_i32, _i32, _i32, _i32, _i32]
+        lib.pcr_ndp_head_rows.restype = _i32
+        lib.pcr_ndp_head_rows.argtypes = [_i32, _i32]
         lib.pcr_ndp_chamfer_scratch_bytes.restype = _i64
         lib.pcr_ndp_chamfer_scratch_bytes.argtypes = [_i32, _i32]
         lib.pcr_ndp_loss_scratch_bytes.restype = _i64
@@ -235,7 +239,8 @@ def load():
 
 def exported_symbols():
     return ["pcr_last_error", "pcr_version", "pcr_workspace_release", "pcr_profile_enable", "pcr_profile_read",
-            "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_featnn_image_chunks", "pcr_ndp_train_partial_floats", "pcr_ndp_chamfer_scratch_bytes",
+            "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_featnn_image_chunks", "pcr_ndp_train_partial_floats", "pcr_ndp_train_partial_floats_head", "pcr_ndp_head_rows",
+            "pcr_ndp_chamfer_scratch_bytes",
             "pcr_ndp_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words", "pcr_ndp_chamfer_max_points",
             "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_attention_scratch_bytes",
             "pcr_offset_attention_scratch_bytes", "pcr_pointnet_scratch_bytes", "pcr_edge_conv_scratch_bytes",

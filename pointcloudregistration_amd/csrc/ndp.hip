@@ -7,7 +7,10 @@
 // cos wz] (w = 2^(m+k0)), h = ReLU(W_in pe + b), depth-1 x h = ReLU(W h + b),
 // r = 1e-3 (W_rot h + b), t = 1e-3 (W_trn h + b), R = exp_so3(r/|r|, |r|),
 // x' = R x + t, and with a nonrigidity branch x' = x + s (x' - x),
-// s = sigmoid(1e-3 (W_nr h + b)).  f32 throughout, as the reference.
+// s = sigmoid(1e-3 (W_nr h + b)).  f32 throughout, as the reference.  That is
+// the SE3 / axis_angle head; the other eight (euler, quaternion and 6D
+// rotations, Sim3 and scene-flow motion; get_Rotation :144-161, rigid_body.py)
+// are written out in ndp_head.h, one kernel instantiation per head.
 //
 // MI355X design: a workgroup of NT = width/32 waves owns 32 points across all
 // levels, wave w computing feature tile w of every layer.  Every layer is a
@@ -25,6 +28,7 @@
 // one 128-byte line.
 #include "pcr_internal.h"
 #include "ndp_tile.h"
+#include "ndp_head.h"
 
 namespace pcr {
 namespace {
@@ -38,7 +42,7 @@ using ndpt::TileX;
 constexpr int kMaxLevels = 16;
 
 struct NdpLevelDev {
-    const float *w_in, *b_in, *w_hid, *b_hid, *w_rot, *b_rot, *w_trn, *b_trn, *w_nr, *b_nr;
+    const float *w_in, *b_in, *w_hid, *b_hid, *w_rot, *b_rot, *w_trn, *b_trn, *w_nr, *b_nr, *w_s, *b_s;
     int m;
 };
 
@@ -53,7 +57,7 @@ struct NdpArgs {
 // earlier level had made NaN a finite nonrigidity where the reference has NaN)
 __device__ __forceinline__ float relu(float v) { return v < 0.0f ? 0.0f : v; }
 
-template <int NT>
+template <int NT, int HEAD>
 __global__ __launch_bounds__(64 * NT) void ndp_warp_kernel(NdpArgs a) {
     constexpr int W = 32 * NT;
     __shared__ TileX X[NT];
@@ -100,50 +104,17 @@ __global__ __launch_bounds__(64 * NT) void ndp_warp_kernel(NdpArgs a) {
         publish(X[w], l, H);
         __syncthreads();
         if (w == 0) {
-            // branches in one 32-row tile: rows 0-2 rotation, 3-5 translation, 6 nonrigidity
+            // branches in one 32-row tile (row map of the head: ndp_head.h)
             const bool has_nr = L.w_nr != nullptr;
-            const float *br = j < 3 ? L.w_rot + j * W
-                            : j < 6 ? L.w_trn + (j - 3) * W
-                            : (j == 6 && has_nr) ? L.w_nr : nullptr;
+            const ndph::BranchW bw{L.w_rot, L.b_rot, L.w_trn, L.b_trn, L.w_nr, L.b_nr, L.w_s, L.b_s};
+            const float *br = ndph::branch_row<HEAD>(bw, j, W);
             f32x16 Bo;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int q = frow(r, h);
-                Bo[r] = q < 3 ? L.b_rot[q] : q < 6 ? L.b_trn[q - 3] : (q == 6 && has_nr) ? L.b_nr[0] : 0.0f;
-            }
+            for (int r = 0; r < 16; ++r) Bo[r] = ndph::branch_bias<HEAD>(bw, frow(r, h));
             Bo = chain<NT>(X, l, [&](int it, int r) { return br ? br[32 * it + frow(r, h)] : 0.0f; }, Bo);
-            // rows 0-3 sit in registers 0-3 of the h=0 half, rows 4-7 in the h=1 half
-            const float o0 = Bo[0], o1 = Bo[1], o2 = Bo[2], o3 = Bo[3];
-            const float p0 = __shfl_xor(o0, 32, 64), p1 = __shfl_xor(o1, 32, 64);
-            const float p2 = __shfl_xor(o2, 32, 64), p3 = __shfl_xor(o3, 32, 64);
-            const float rr0 = h ? p0 : o0, rr1 = h ? p1 : o1, rr2 = h ? p2 : o2;
-            const float tt0 = h ? p3 : o3, tt1 = h ? o0 : p0, tt2 = h ? o1 : p1;
-            const float nrr = h ? o2 : p2;
-            const float t0 = 0.001f * tt0, t1 = 0.001f * tt1, t2 = 0.001f * tt2;
-            const float r0 = 0.001f * rr0, r1 = 0.001f * rr1, r2 = 0.001f * rr2;
-            const float th = sqrtf((r0 * r0 + r1 * r1) + r2 * r2);
-            const float w0 = r0 / th, w1 = r1 / th, w2 = r2 / th;
-            // K = skew(w): [[0,-w2,w1],[w2,0,-w0],[-w1,w0,0]]
-            const float K[3][3] = {{0.f, -w2, w1}, {w2, 0.f, -w0}, {-w1, w0, 0.f}};
-            const float sn = sinf(th), cs = 1.0f - cosf(th);
-            float R[3][3];
-#pragma unroll
-            for (int u = 0; u < 3; ++u)
-#pragma unroll
-                for (int v = 0; v < 3; ++v) {
-                    const float kk = (K[u][0] * K[0][v] + K[u][1] * K[1][v]) + K[u][2] * K[2][v];
-                    R[u][v] = ((u == v ? 1.0f : 0.0f) + sn * K[u][v]) + cs * kk;
-                }
-            float n0 = ((R[0][0] * x0 + R[0][1] * x1) + R[0][2] * x2) + t0;
-            float n1 = ((R[1][0] * x0 + R[1][1] * x1) + R[1][2] * x2) + t1;
-            float n2 = ((R[2][0] * x0 + R[2][1] * x1) + R[2][2] * x2) + t2;
-            float sg = 0.0f;
-            if (has_nr) {
-                sg = 1.0f / (1.0f + expf(-(0.001f * nrr)));
-                n0 = x0 + sg * (n0 - x0);
-                n1 = x1 + sg * (n1 - x1);
-                n2 = x2 + sg * (n2 - x2);
-            }
+            ndph::HeadOut<HEAD> ho;
+            ndph::head_forward<HEAD>(Bo, h, has_nr, x0, x1, x2, ho);
+            const float n0 = ho.n[0], n1 = ho.n[1], n2 = ho.n[2], sg = ho.s;
             if (h == 0) {
                 xn[0][j] = n0; xn[1][j] = n1; xn[2][j] = n2;
                 if (valid) {
@@ -184,22 +155,39 @@ extern "C" int pcr_ndp_warp(const float *x, int32_t N, const pcr_ndp_level *leve
     pcr::NdpArgs a;
     a.x = x; a.N = N; a.nlev = n_levels; a.depth = depth; a.k0 = k0;
     a.x_out = x_out; a.x_levels = x_levels; a.nonrig = nonrigidity;
+    const int head = n_levels ? levels[0].head : 0;
+    PCR_REQUIRE(pcr::ndph::head_valid(head), PCR_ERR_ARG, "ndp_warp: unknown head code %d", head);
+    const int motion = pcr::ndph::head_motion(head);
     for (int i = 0; i < n_levels; ++i) {
         const pcr_ndp_level &s = levels[i];
-        PCR_REQUIRE(s.w_in && s.b_in && s.w_rot && s.b_rot && s.w_trn && s.b_trn &&
-                        (depth == 1 || (s.w_hid && s.b_hid)) && (!s.w_nr || s.b_nr),
+        PCR_REQUIRE(s.head == head, PCR_ERR_ARG, "ndp_warp: level %d has head code %d, level 0 has %d (%s)", i,
+                    s.head, head, pcr::ndph::head_name(head));
+        PCR_REQUIRE(s.w_in && s.b_in && s.w_trn && s.b_trn && (depth == 1 || (s.w_hid && s.b_hid)) &&
+                        (!s.w_nr || s.b_nr),
                     PCR_ERR_ARG, "ndp_warp: level %d has a null weight", i);
-        a.lv[i] = pcr::NdpLevelDev{s.w_in, s.b_in, s.w_hid, s.b_hid, s.w_rot, s.b_rot,
-                                   s.w_trn, s.b_trn, s.w_nr, s.b_nr, s.m};
+        PCR_REQUIRE(motion == pcr::ndph::kSflow || (s.w_rot && s.b_rot), PCR_ERR_ARG,
+                    "ndp_warp: level %d of head %s has no rotation branch", i, pcr::ndph::head_name(head));
+        PCR_REQUIRE(motion != pcr::ndph::kSim3 || (s.w_s && s.b_s), PCR_ERR_ARG,
+                    "ndp_warp: level %d of head %s has no scale branch (w_s, b_s)", i, pcr::ndph::head_name(head));
+        a.lv[i] = pcr::NdpLevelDev{s.w_in, s.b_in, s.w_hid, s.b_hid, s.w_rot, s.b_rot, s.w_trn,
+                                   s.b_trn, s.w_nr, s.b_nr, s.w_s, s.b_s, s.m};
     }
     hipStream_t st = pcr::as_stream(stream);
     const dim3 g((unsigned)((N + 31) / 32));  // 32 points per workgroup, a wave per feature tile
-    switch (width / 32) {
-        case 1: hipLaunchKernelGGL(pcr::ndp_warp_kernel<1>, g, dim3(64), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(pcr::ndp_warp_kernel<2>, g, dim3(128), 0, st, a); break;
-        case 3: hipLaunchKernelGGL(pcr::ndp_warp_kernel<3>, g, dim3(192), 0, st, a); break;
-        default: hipLaunchKernelGGL(pcr::ndp_warp_kernel<4>, g, dim3(256), 0, st, a); break;
+#define PCR_NDP_WARP(HEAD)                                                                             \
+    case HEAD:                                                                                         \
+        switch (width / 32) {                                                                          \
+            case 1: hipLaunchKernelGGL((pcr::ndp_warp_kernel<1, HEAD>), g, dim3(64), 0, st, a); break;  \
+            case 2: hipLaunchKernelGGL((pcr::ndp_warp_kernel<2, HEAD>), g, dim3(128), 0, st, a); break; \
+            case 3: hipLaunchKernelGGL((pcr::ndp_warp_kernel<3, HEAD>), g, dim3(192), 0, st, a); break; \
+            default: hipLaunchKernelGGL((pcr::ndp_warp_kernel<4, HEAD>), g, dim3(256), 0, st, a); break; \
+        }                                                                                              \
+        break;
+    switch (head) {
+        PCR_NDP_WARP(0) PCR_NDP_WARP(1) PCR_NDP_WARP(2) PCR_NDP_WARP(3) PCR_NDP_WARP(4)
+        PCR_NDP_WARP(5) PCR_NDP_WARP(6) PCR_NDP_WARP(7) PCR_NDP_WARP(8)
     }
+#undef PCR_NDP_WARP
     PCR_LAUNCH_CHECK();
     return PCR_OK;
 }

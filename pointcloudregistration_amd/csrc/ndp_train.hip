@@ -18,6 +18,11 @@
 //   GEMMs (K = points) read contiguous rows.
 //   aux [8][N]: r (3, = 1e-3 o_r), y = R x + t (3), s (nonrigidity), 0.
 //   dO [8][N]: dL/d(branch pre-activation): rot (3), trn (3), nr (1), 0.
+//   That is head 0 (SE3 / axis_angle).  The other eight heads of NDPLayer
+//   (euler, quaternion, 6D; Sim3, sflow) use 16 rows -- rot 0-5, trn 6-8, nr 9,
+//   scale 10, in aux also R x of a Sim3 head in 11-13 -- and their forward and
+//   chain rule are written out at the top of ndp_head.h; one instantiation of
+//   ndp_train_fwd / ndp_train_bwd per head.
 // MFMA mapping (ndp_tile.h): a 32-feature x 32-point tile is 16 accumulator
 // registers, a layer a chain of exact-f32 v_mfma_f32_32x32x2_f32 whose B operand
 // is the previous layer's tile; a workgroup of 4 waves owns 32 points, wave w
@@ -29,6 +34,7 @@
 // (deterministic).
 #include "pcr_internal.h"
 #include "ndp_tile.h"
+#include "ndp_head.h"
 #include "ndp_ctl.h"
 #include <cstdlib>
 
@@ -49,15 +55,16 @@ struct TrainArgs {
     int N, W, nhid, m, k0;          // nhid = depth - 1
     const float *w_in, *b_in;       // (W, 6), (W)
     const float *w_hid[kMaxHid], *b_hid[kMaxHid];  // (W, W), (W)
-    const float *w_rot, *b_rot, *w_trn, *b_trn, *w_nr, *b_nr;
+    const float *w_rot, *b_rot, *w_trn, *b_trn, *w_nr, *b_nr, *w_s, *b_s;
+    int head;                       // head code (ndp_head.h)
     float *pe;                      // [6][N]
     float *H;                       // [nhid + 1][W][N]: H_0 = relu(input), H_l = relu(hidden l)
-    float *aux;                     // [8][N]
+    float *aux;                     // [8][N], or [16][N] (heads 1-8)
     float *x_out;                   // (N, 3)
     // backward
     const float *g;                 // (N, 3) dL/dx'
     double bce_scale;               // w_reg / N when the level has the nonrigidity branch, else 0
-    float *dO;                      // [8][N]
+    float *dO;                      // [8][N], or [16][N]
     float *D;                       // [nhid + 1][W][N]: dL/d(pre-activation) of layer l
     // Chamfer subset (optional): inv[p] = k when inds[k] == p (inds unique), else -1;
     // the forward also writes x'[inds] to xs (K, 3), and the backward reads dL/dx'
@@ -73,6 +80,7 @@ struct TrainArgs {
 __device__ __forceinline__ float sgn_mask(float a, float d) { return a > 0.0f ? d : 0.0f; }
 
 // ---- forward of one level, saving what the backward needs -------------------
+template <int HEAD>
 __global__ __launch_bounds__(64 * kNT) void ndp_train_fwd(TrainArgs a) {
     if (gated_off(a.gate)) return;
     constexpr int W = 32 * kNT;
@@ -128,51 +136,33 @@ __global__ __launch_bounds__(64 * kNT) void ndp_train_fwd(TrainArgs a) {
     __syncthreads();
     if (w != 0) return;  // branch head and warp: wave 0 (no barrier follows)
     const bool has_nr = a.w_nr != nullptr;
-    const float *br = j < 3 ? a.w_rot + j * W
-                    : j < 6 ? a.w_trn + (j - 3) * W
-                    : (j == 6 && has_nr) ? a.w_nr : nullptr;
+    constexpr ndph::RowMap M = ndph::row_map(HEAD);
+    const ndph::BranchW bw{a.w_rot, a.b_rot, a.w_trn, a.b_trn, a.w_nr, a.b_nr, a.w_s, a.b_s};
+    const float *br = ndph::branch_row<HEAD>(bw, j, W);
     f32x16 Bo;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int q = frow(r, h);
-        Bo[r] = q < 3 ? a.b_rot[q] : q < 6 ? a.b_trn[q - 3] : (q == 6 && has_nr) ? a.b_nr[0] : 0.0f;
-    }
+    for (int r = 0; r < 16; ++r) Bo[r] = ndph::branch_bias<HEAD>(bw, frow(r, h));
     Bo = chain<kNT>(X, l, [&](int it, int r) { return br ? br[32 * it + frow(r, h)] : 0.0f; }, Bo);
-    const float o0 = Bo[0], o1 = Bo[1], o2 = Bo[2], o3 = Bo[3];
-    const float p0 = __shfl_xor(o0, 32, 64), p1 = __shfl_xor(o1, 32, 64);
-    const float p2 = __shfl_xor(o2, 32, 64), p3 = __shfl_xor(o3, 32, 64);
-    const float rr0 = h ? p0 : o0, rr1 = h ? p1 : o1, rr2 = h ? p2 : o2;
-    const float tt0 = h ? p3 : o3, tt1 = h ? o0 : p0, tt2 = h ? o1 : p1;
-    const float nrr = h ? o2 : p2;
-    const float t0 = 0.001f * tt0, t1 = 0.001f * tt1, t2 = 0.001f * tt2;
-    const float r0 = 0.001f * rr0, r1 = 0.001f * rr1, r2 = 0.001f * rr2;
-    const float th = sqrtf((r0 * r0 + r1 * r1) + r2 * r2);
-    const float w0 = r0 / th, w1 = r1 / th, w2 = r2 / th;
-    const float K[3][3] = {{0.f, -w2, w1}, {w2, 0.f, -w0}, {-w1, w0, 0.f}};
-    const float sn = sinf(th), cs = 1.0f - cosf(th);
-    float R[3][3];
-#pragma unroll
-    for (int u = 0; u < 3; ++u)
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            const float kk = (K[u][0] * K[0][v] + K[u][1] * K[1][v]) + K[u][2] * K[2][v];
-            R[u][v] = ((u == v ? 1.0f : 0.0f) + sn * K[u][v]) + cs * kk;
-        }
-    const float y0 = ((R[0][0] * x0 + R[0][1] * x1) + R[0][2] * x2) + t0;
-    const float y1 = ((R[1][0] * x0 + R[1][1] * x1) + R[1][2] * x2) + t1;
-    const float y2 = ((R[2][0] * x0 + R[2][1] * x1) + R[2][2] * x2) + t2;
-    float n0 = y0, n1 = y1, n2 = y2, s = 0.0f;
-    if (has_nr) {
-        s = 1.0f / (1.0f + expf(-(0.001f * nrr)));
-        n0 = x0 + s * (y0 - x0);
-        n1 = x1 + s * (y1 - x1);
-        n2 = x2 + s * (y2 - x2);
-    }
+    ndph::HeadOut<HEAD> ho;
+    ndph::head_forward<HEAD>(Bo, h, has_nr, x0, x1, x2, ho);
+    const float n0 = ho.n[0], n1 = ho.n[1], n2 = ho.n[2];
     if (valid && h == 0) {
         a.x_out[3 * pt] = n0; a.x_out[3 * pt + 1] = n1; a.x_out[3 * pt + 2] = n2;
-        const float v[8] = {r0, r1, r2, y0, y1, y2, s, 0.0f};
+        float v[M.n];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) a.aux[(size_t)k * N + pt] = v[k];
+        for (int k = 0; k < M.n; ++k) v[k] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < M.rot; ++k) v[k] = ho.r[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[M.trn + k] = ho.y[k];
+        v[M.nr] = ho.s;
+        if constexpr (ndph::head_motion(HEAD) == ndph::kSim3) {
+            v[M.sc] = ho.c;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[M.rx + k] = ho.rx[k];
+        }
+#pragma unroll
+        for (int k = 0; k < M.n; ++k) a.aux[(size_t)k * N + pt] = v[k];
         if (a.xs) {
             const int k = a.inv[pt];
             if (k >= 0) { a.xs[3 * k] = n0; a.xs[3 * k + 1] = n1; a.xs[3 * k + 2] = n2; }
@@ -181,6 +171,7 @@ __global__ __launch_bounds__(64 * kNT) void ndp_train_fwd(TrainArgs a) {
 }
 
 // ---- backward of one level: dL/dx' -> branch gradients -> layer deltas -----
+template <int HEAD>
 __global__ __launch_bounds__(64 * kNT) void ndp_train_bwd(TrainArgs a) {
     if (gated_off(a.gate)) return;
     constexpr int W = 32 * kNT;
@@ -193,8 +184,12 @@ __global__ __launch_bounds__(64 * kNT) void ndp_train_bwd(TrainArgs a) {
     // per-point branch gradients: computed once per workgroup by wave 0 (its two
     // half-waves split the gradient replicas) and broadcast through LDS to the
     // four waves (each had recomputed them, 96 gradient words per lane)
-    __shared__ float sdO[8][32];
-    float dO[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    constexpr ndph::RowMap M = ndph::row_map(HEAD);
+    constexpr int motion = ndph::head_motion(HEAD);
+    __shared__ float sdO[M.n][32];
+    float dO[M.n];
+#pragma unroll
+    for (int k = 0; k < M.n; ++k) dO[k] = 0.0f;
     if (w == 0) {
         const float x[3] = {valid ? a.x[3 * pt] : 0.f, valid ? a.x[3 * pt + 1] : 0.f, valid ? a.x[3 * pt + 2] : 0.f};
         float g[3] = {0.f, 0.f, 0.f};
@@ -232,83 +227,65 @@ __global__ __launch_bounds__(64 * kNT) void ndp_train_bwd(TrainArgs a) {
         } else {
             g[0] = a.g[3 * pt]; g[1] = a.g[3 * pt + 1]; g[2] = a.g[3 * pt + 2];
         }
-        float aux[7];
+        float aux[M.n];
 #pragma unroll
-        for (int k = 0; k < 7; ++k) aux[k] = valid ? a.aux[(size_t)k * N + pt] : 0.f;
-        const float r0 = aux[0], r1 = aux[1], r2 = aux[2];
-        const float y[3] = {aux[3], aux[4], aux[5]};
+        for (int k = 0; k < M.n; ++k) aux[k] = valid ? a.aux[(size_t)k * N + pt] : 0.f;
+        const float y[3] = {aux[M.trn], aux[M.trn + 1], aux[M.trn + 2]};
         if (has_nr) {
             // x' = x + s (y - x), s = sigmoid(1e-3 o_n); BCE(s, 0) = -log(1 - s), mean
-            const float s = aux[6];
+            const float s = aux[M.nr];
             const float ds = ((g[0] * (y[0] - x[0]) + g[1] * (y[1] - x[1])) + g[2] * (y[2] - x[2])) +
                              (float)a.bce_scale / (1.0f - s);
-            dO[6] = 0.001f * (ds * (s * (1.0f - s)));
+            dO[M.nr] = 0.001f * (ds * (s * (1.0f - s)));
             g[0] *= s; g[1] *= s; g[2] *= s;
         }
-        // y = R x + t
-        dO[3] = 0.001f * g[0]; dO[4] = 0.001f * g[1]; dO[5] = 0.001f * g[2];
-        const float th = sqrtf((r0 * r0 + r1 * r1) + r2 * r2);
-        const float w[3] = {r0 / th, r1 / th, r2 / th};
-        const float K[3][3] = {{0.f, -w[2], w[1]}, {w[2], 0.f, -w[0]}, {-w[1], w[0], 0.f}};
-        const float sn = sinf(th), cs0 = cosf(th), cs = 1.0f - cs0;
-        float G[3][3], KK[3][3];
-#pragma unroll
-        for (int u = 0; u < 3; ++u)
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                G[u][v] = g[u] * x[v];
-                KK[u][v] = (K[u][0] * K[0][v] + K[u][1] * K[1][v]) + K[u][2] * K[2][v];
+        // y = R x + t (SE3), c R x + t (Sim3), x + t (sflow)
+        dO[M.trn] = 0.001f * g[0]; dO[M.trn + 1] = 0.001f * g[1]; dO[M.trn + 2] = 0.001f * g[2];
+        if constexpr (motion != ndph::kSflow) {
+            if constexpr (motion == ndph::kSim3) {
+                const float c = aux[M.sc];
+                dO[M.sc] = 0.001f * ((g[0] * aux[M.rx] + g[1] * aux[M.rx + 1]) + g[2] * aux[M.rx + 2]);
+                g[0] *= c; g[1] *= c; g[2] *= c;
             }
-        // R = I + sin(th) K + (1 - cos(th)) K^2
-        float dth = 0.0f;
-        float dK[3][3];
+            float G[3][3], dr[6];
 #pragma unroll
-        for (int u = 0; u < 3; ++u)
+            for (int u = 0; u < 3; ++u)
 #pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                dth += G[u][v] * (cs0 * K[u][v] + sn * KK[u][v]);
-                // d<G, K K>/dK = G K^T + K^T G
-                float gkt = 0.0f, ktg = 0.0f;
+                for (int v = 0; v < 3; ++v) G[u][v] = g[u] * x[v];
+            ndph::rotation_bwd<ndph::head_format(HEAD)>(aux, G, dr);
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    gkt += G[u][q] * K[v][q];
-                    ktg += K[q][u] * G[q][v];
-                }
-                dK[u][v] = sn * G[u][v] + cs * (gkt + ktg);
-            }
-        const float gw[3] = {dK[2][1] - dK[1][2], dK[0][2] - dK[2][0], dK[1][0] - dK[0][1]};
-        const float gww = (gw[0] * w[0] + gw[1] * w[1]) + gw[2] * w[2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) dO[c] = 0.001f * ((gw[c] - gww * w[c]) / th + dth * w[c]);
+            for (int c = 0; c < M.rot; ++c) dO[c] = 0.001f * dr[c];
+        }
         if (!valid)
 #pragma unroll
-            for (int k = 0; k < 8; ++k) dO[k] = 0.0f;
-        if (h == 0) {  // (w is the rotation axis here)
+            for (int k = 0; k < M.n; ++k) dO[k] = 0.0f;
+        if (h == 0) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) sdO[k][j] = dO[k];
+            for (int k = 0; k < M.n; ++k) sdO[k][j] = dO[k];
             if (valid)
-                for (int k = 0; k < 8; ++k) a.dO[(size_t)k * N + pt] = dO[k];
+#pragma unroll
+                for (int k = 0; k < M.n; ++k) a.dO[(size_t)k * N + pt] = dO[k];
         }
     }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 8; ++k) dO[k] = sdO[k][j];
-    // delta of the last hidden activation: W_b^T dO (K = 8 branch rows, 4 k-steps)
+    for (int k = 0; k < M.n; ++k) dO[k] = sdO[k][j];
+    // delta of the last hidden activation: W_b^T dO (K = the head's branch rows
+    // rounded up to even: 8 rows, 4 k-steps for head 0; 12 rows, 6 k-steps otherwise)
     const int L = a.nhid;
     auto load_act = [&](int layer, int r) -> float {
         return valid ? a.H[((size_t)layer * W + 32 * w + frow(r, h)) * N + pt] : 0.0f;
     };
-    auto branch_w = [&](int q, int col) -> float {  // W_b[q][col], q = branch row 0..7
-        if (q < 3) return a.w_rot[q * W + col];
-        if (q < 6) return a.w_trn[(q - 3) * W + col];
-        if (q == 6 && has_nr) return a.w_nr[col];
-        return 0.0f;
+    const ndph::BranchW bw{a.w_rot, a.b_rot, a.w_trn, a.b_trn, a.w_nr, a.b_nr, a.w_s, a.b_s};
+    auto branch_w = [&](int q, int col) -> float {  // W_b[q][col], q = branch row
+        const float *row = ndph::branch_row<HEAD>(bw, q, W);
+        return row ? row[col] : 0.0f;
     };
     f32x16 Dt;
 #pragma unroll
     for (int r = 0; r < 16; ++r) Dt[r] = 0.0f;
 #pragma unroll
-    for (int s = 0; s < 4; ++s)  // k = 2s + h: B[k][j] = dO[k] of point j
+    for (int s = 0; s < (M.nw + 1) / 2; ++s)  // k = 2s + h: B[k][j] = dO[k] of point j
         Dt = __builtin_amdgcn_mfma_f32_32x32x2f32(branch_w(2 * s + h, 32 * w + j),
                                                   h ? dO[2 * s + 1] : dO[2 * s], Dt, 0, 0, 0);
     // rows of the transposed product: A[i][k] = W[k][i] -> lane j gives W[k][32 w + j]
@@ -586,8 +563,14 @@ static int fill_train(const pcr_ndp_train *t, pcr::TrainArgs &a) {
     PCR_REQUIRE(t->N >= 0 && t->width == 128, PCR_ERR_ARG, "ndp_train: width %d (only 128)", t->width);
     PCR_REQUIRE(t->depth >= 1 && t->depth - 1 <= pcr::kMaxHid, PCR_ERR_ARG, "ndp_train: depth %d", t->depth);
     const pcr_ndp_level &L = t->level;
-    PCR_REQUIRE(L.w_in && L.b_in && L.w_rot && L.b_rot && L.w_trn && L.b_trn && (!L.w_nr || L.b_nr),
-                PCR_ERR_ARG, "ndp_train: null weight");
+    PCR_REQUIRE(pcr::ndph::head_valid(L.head), PCR_ERR_ARG, "ndp_train: unknown head code %d", L.head);
+    const int motion = pcr::ndph::head_motion(L.head);
+    PCR_REQUIRE(L.w_in && L.b_in && L.w_trn && L.b_trn && (!L.w_nr || L.b_nr), PCR_ERR_ARG,
+                "ndp_train: null weight (head %s)", pcr::ndph::head_name(L.head));
+    PCR_REQUIRE(motion == pcr::ndph::kSflow || (L.w_rot && L.b_rot), PCR_ERR_ARG,
+                "ndp_train: head %s without the rotation branch", pcr::ndph::head_name(L.head));
+    PCR_REQUIRE(motion != pcr::ndph::kSim3 || (L.w_s && L.b_s), PCR_ERR_ARG,
+                "ndp_train: head %s without the scale branch (w_s, b_s)", pcr::ndph::head_name(L.head));
     a = pcr::TrainArgs{};
     a.x = t->x; a.N = t->N; a.W = t->width; a.nhid = t->depth - 1; a.m = L.m; a.k0 = t->k0;
     a.w_in = L.w_in; a.b_in = L.b_in;
@@ -597,7 +580,7 @@ static int fill_train(const pcr_ndp_train *t, pcr::TrainArgs &a) {
         a.b_hid[k] = t->b_hid[k];
     }
     a.w_rot = L.w_rot; a.b_rot = L.b_rot; a.w_trn = L.w_trn; a.b_trn = L.b_trn;
-    a.w_nr = L.w_nr; a.b_nr = L.b_nr;
+    a.w_nr = L.w_nr; a.b_nr = L.b_nr; a.w_s = L.w_s; a.b_s = L.b_s; a.head = L.head;
     a.pe = t->pe; a.H = t->H; a.aux = t->aux; a.x_out = t->x_out;
     a.g = t->g; a.bce_scale = t->bce_scale; a.dO = t->dO; a.D = t->D;
     a.inv = t->inv; a.xs = t->xs; a.gsub = t->gsub; a.gacc = t->gacc; a.gacc_k = t->gacc_k;
@@ -613,8 +596,16 @@ extern "C" int pcr_ndp_train_forward(const pcr_ndp_train *t, pcr_stream_t stream
     if (a.N == 0) return PCR_OK;
     PCR_REQUIRE(a.x && a.pe && a.H && a.aux && a.x_out, PCR_ERR_ARG, "ndp_train_forward: null buffer");
     PCR_REQUIRE(!a.xs || a.inv, PCR_ERR_ARG, "ndp_train_forward: xs without inv");
-    hipLaunchKernelGGL(pcr::ndp_train_fwd, dim3((a.N + 31) / 32), dim3(64 * pcr::kNT), 0,
-                       pcr::as_stream(stream), a);
+#define PCR_NDP_FWD(HEAD)                                                                        \
+    case HEAD:                                                                                   \
+        hipLaunchKernelGGL(pcr::ndp_train_fwd<HEAD>, dim3((a.N + 31) / 32), dim3(64 * pcr::kNT), 0, \
+                           pcr::as_stream(stream), a);                                           \
+        break;
+    switch (a.head) {
+        PCR_NDP_FWD(0) PCR_NDP_FWD(1) PCR_NDP_FWD(2) PCR_NDP_FWD(3) PCR_NDP_FWD(4)
+        PCR_NDP_FWD(5) PCR_NDP_FWD(6) PCR_NDP_FWD(7) PCR_NDP_FWD(8)
+    }
+#undef PCR_NDP_FWD
     PCR_LAUNCH_CHECK();
     return PCR_OK;
 }
@@ -630,9 +621,17 @@ extern "C" int pcr_ndp_train_backward(const pcr_ndp_train *t, float *part, int32
                 "ndp_train_backward: null buffer");
     PCR_REQUIRE(chunk >= 64 && chunk % 64 == 0, PCR_ERR_ARG, "ndp_train_backward: chunk %d", chunk);
     hipStream_t s = pcr::as_stream(stream);
-    hipLaunchKernelGGL(pcr::ndp_train_bwd, dim3((a.N + 31) / 32), dim3(64 * pcr::kNT), 0, s, a);
+#define PCR_NDP_BWD(HEAD)                                                                              \
+    case HEAD:                                                                                         \
+        hipLaunchKernelGGL(pcr::ndp_train_bwd<HEAD>, dim3((a.N + 31) / 32), dim3(64 * pcr::kNT), 0, s, a); \
+        break;
+    switch (a.head) {
+        PCR_NDP_BWD(0) PCR_NDP_BWD(1) PCR_NDP_BWD(2) PCR_NDP_BWD(3) PCR_NDP_BWD(4)
+        PCR_NDP_BWD(5) PCR_NDP_BWD(6) PCR_NDP_BWD(7) PCR_NDP_BWD(8)
+    }
+#undef PCR_NDP_BWD
     PCR_LAUNCH_CHECK();
-    // jobs: input layer (W x 6 over pe), hidden layers, branches (7 x W over H_last)
+    // jobs: input layer (W x 6 over pe), hidden layers, branches (7 or 11 x W over H_last)
     const int W = a.W, N = a.N, nchunk = (N + chunk - 1) / chunk;
     pcr::WgradArgs wa{};
     pcr::ReduceArgs ra{};
@@ -646,13 +645,13 @@ extern "C" int pcr_ndp_train_backward(const pcr_ndp_train *t, float *part, int32
         off += (size_t)nchunk * ((size_t)FO * FI + FO);
         ++nj;
     };
-    // grads: [0] w_in [1] b_in, then per hidden layer (w, b), then w_branch (8 x W rows
-    // rot 0-2, trn 3-5, nr 6), b_branch (8)
+    // grads: [0] w_in [1] b_in, then per hidden layer (w, b), then w_branch (the head's
+    // gradient rows x W: rot 0-2, trn 3-5, nr 6 for head 0), b_branch
     add(a.D, a.pe, W, 6, grads[0], grads[1]);
     for (int k = 0; k < a.nhid; ++k)
         add(a.D + (size_t)(k + 1) * W * N, a.H + (size_t)k * W * N, W, W, grads[2 + 2 * k],
             grads[3 + 2 * k]);
-    add(a.dO, a.H + (size_t)a.nhid * W * N, 7, W, grads[2 + 2 * a.nhid], grads[3 + 2 * a.nhid]);
+    add(a.dO, a.H + (size_t)a.nhid * W * N, pcr::ndph::row_map(a.head).nw, W, grads[2 + 2 * a.nhid], grads[3 + 2 * a.nhid]);
     hipLaunchKernelGGL(pcr::ndp_wgrad, dim3(nchunk, nj), dim3(1024), 0, s, wa);
     PCR_LAUNCH_CHECK();
     hipLaunchKernelGGL(pcr::ndp_wgrad_reduce, dim3((W * W + W + 63) / 64, nj), dim3(256), 0, s, ra);
@@ -660,10 +659,31 @@ extern "C" int pcr_ndp_train_backward(const pcr_ndp_train *t, float *part, int32
     return PCR_OK;
 }
 
+extern "C" int64_t pcr_ndp_train_partial_floats_head(int32_t N, int32_t width, int32_t depth, int32_t chunk,
+                                                     int32_t head) {
+    if (N <= 0 || chunk <= 0 || !pcr::ndph::head_valid(head)) return 0;
+    const int64_t nchunk = (N + chunk - 1) / chunk, W = width, B = pcr::ndph::row_map(head).nw;
+    return nchunk * ((W * 6 + W) + (int64_t)(depth - 1) * (W * W + W) + (B * W + B));
+}
+
 extern "C" int64_t pcr_ndp_train_partial_floats(int32_t N, int32_t width, int32_t depth, int32_t chunk) {
-    if (N <= 0 || chunk <= 0) return 0;
-    const int64_t nchunk = (N + chunk - 1) / chunk, W = width;
-    return nchunk * ((W * 6 + W) + (int64_t)(depth - 1) * (W * W + W) + (7 * W + 7));
+    return pcr_ndp_train_partial_floats_head(N, width, depth, chunk, 0);
+}
+
+extern "C" int32_t pcr_ndp_head_rows(int32_t head, int32_t what) {
+    if (!pcr::ndph::head_valid(head)) return -1;
+    const pcr::ndph::RowMap m = pcr::ndph::row_map(head);
+    const bool sim3 = pcr::ndph::head_motion(head) == pcr::ndph::kSim3;
+    switch (what) {
+        case 0: return m.rot;
+        case 1: return m.n;
+        case 2: return m.nw;
+        case 3: return m.trn;
+        case 4: return m.nr;
+        case 5: return sim3 ? m.sc : -1;
+        case 6: return sim3 ? m.rx : -1;
+        default: return -1;
+    }
 }
 
 extern "C" int pcr_ndp_chamfer_glue(const float *d1, int32_t K, const float *d2, int32_t M,

@@ -7,8 +7,12 @@ takes the layers' modules or state dicts directly.  Both return
 (x, data) with data[i] = (x after level i, nonrigidity of level i or None),
 as the reference.  Every level runs in one libpcr launch (pcr_ndp_warp);
 the NDP optimisation loop itself (forward + backward per iteration) stays in
-torch.  Supported: motion "SE3" with rotation
-"axis_angle" (config/NDP.yaml), width in {32, 64, 96, 128}.
+torch.  Supported: every head of the reference's NDPLayer
+-- motion "SE3", "Sim3" or "sflow" with rotation "axis_angle", "euler",
+"quaternion" or "6D" (config/NDP.yaml ships SE3 / axis_angle) -- and width in
+{32, 64, 96, 128}.  A module carries its head (`motion`, `rotation_format`);
+for state dicts pass `motion=` / `rotation_format=`.  All levels of a stack
+share one head, as in the reference.
 """
 from __future__ import annotations
 
@@ -21,35 +25,53 @@ from . import _lib
 
 _PTRS = ("w_in", "b_in", "w_hid", "b_hid", "w_rot", "b_rot", "w_trn", "b_trn", "w_nr", "b_nr")
 
+MOTIONS = ("SE3", "Sim3", "sflow")
+ROTATION_FORMATS = ("axis_angle", "euler", "quaternion", "6D")
+ROT_ROWS = {"axis_angle": 3, "euler": 3, "quaternion": 4, "6D": 6}
+
 
 class _Level(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in _PTRS] + [("m", ctypes.c_int32),
-                                                        ("reserved", ctypes.c_int32)]
+    """pcr_ndp_level (include/pcr_api.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in _PTRS] + \
+        [("m", ctypes.c_int32), ("reserved", ctypes.c_int32), ("w_s", ctypes.c_void_p),
+         ("b_s", ctypes.c_void_p), ("head", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
 
 
-def _state(layer):
+def head_code(motion="SE3", rotation_format="axis_angle"):
+    """PCR_NDP_HEAD(motion, rotation): 0 = SE3 / axis_angle ... 8 = sflow."""
+    if motion not in MOTIONS:
+        raise ValueError(f"motion {motion!r} not in {MOTIONS}")
+    if motion == "sflow":
+        return 8
+    if rotation_format not in ROTATION_FORMATS:
+        raise ValueError(f"rotation_format {rotation_format!r} not in {ROTATION_FORMATS}")
+    return 4 * MOTIONS.index(motion) + ROTATION_FORMATS.index(rotation_format)
+
+
+def _state(layer, motion=None, rotation_format=None):
+    """(state dict, m, k0, head code) of a module or a state dict; explicit
+    keywords override what a module says."""
     if hasattr(layer, "state_dict"):
-        if getattr(layer, "motion", "SE3") != "SE3" or \
-                getattr(layer, "rotation_format", "axis_angle") != "axis_angle":
-            raise NotImplementedError("pcr_ndp_warp implements motion SE3 + axis_angle (C5)")
-        return layer.state_dict(), getattr(layer, "m", None), getattr(layer, "k0", None)
-    return layer, None, None
+        mo = motion if motion is not None else getattr(layer, "motion", "SE3")
+        rf = rotation_format if rotation_format is not None else getattr(layer, "rotation_format", "axis_angle")
+        return layer.state_dict(), getattr(layer, "m", None), getattr(layer, "k0", None), head_code(mo, rf)
+    return layer, None, None, head_code(motion or "SE3", rotation_format or "axis_angle")
 
 
 class PreparedPyramid:
     """Device-resident weights + level descriptors, built once (no per-call
     host copies); `warp` then costs one launch."""
 
-    def __init__(self, levels, k0=-8, ms=None, device=None):
+    def __init__(self, levels, k0=-8, ms=None, device=None, motion=None, rotation_format=None):
         dev = torch.device(device) if device is not None else torch.device("cuda")
         self.device, self.k0 = dev, k0
         self._keep, self.structs, self.width, self.depth = [], [], None, None
         for i, layer in enumerate(levels):
-            sd, m_mod, k0_mod = _state(layer)
+            sd, m_mod, k0_mod, head = _state(layer, motion, rotation_format)
             if k0_mod is not None:
                 self.k0 = k0_mod
             m = ms[i] if ms is not None else (m_mod if m_mod is not None else i + 1)
-            st = self._level(sd, int(m))
+            st = self._level(sd, int(m), head)
             self.structs.append(st)
 
     def _as_dev(self, v):
@@ -61,7 +83,7 @@ class PreparedPyramid:
         self._keep.append(t)
         return t
 
-    def _level(self, sd, m):
+    def _level(self, sd, m, head=0):
         w_in = self._dev(sd["input.0.weight"])
         W = w_in.shape[0]
         hid = []
@@ -78,7 +100,17 @@ class PreparedPyramid:
             wh = self._dev(torch.stack([self._as_dev(sd[f"mlp.pts_linears.{k}.weight"]) for k in hid]))
             bh = self._dev(torch.stack([self._as_dev(sd[f"mlp.pts_linears.{k}.bias"]) for k in hid]))
             st.w_hid, st.b_hid = wh.data_ptr(), bh.data_ptr()
-        st.w_rot, st.b_rot = self._dev(sd["rot_brach.weight"]).data_ptr(), self._dev(sd["rot_brach.bias"]).data_ptr()
+        st.head = head
+        if head != 8:  # sflow has no rotation branch
+            rows = (3, 3, 4, 6)[head & 3]
+            if "rot_brach.weight" not in sd or tuple(sd["rot_brach.weight"].shape) != (rows, W):
+                raise ValueError(f"rotation format {ROTATION_FORMATS[head & 3]!r} needs a ({rows}, {W}) "
+                                 "rot_brach.weight")
+            st.w_rot, st.b_rot = self._dev(sd["rot_brach.weight"]).data_ptr(), self._dev(sd["rot_brach.bias"]).data_ptr()
+        if head >> 2 == 1:  # Sim3: the scale branch
+            if "s_branch.weight" not in sd:
+                raise ValueError("motion 'Sim3' needs s_branch.weight / s_branch.bias")
+            st.w_s, st.b_s = self._dev(sd["s_branch.weight"]).data_ptr(), self._dev(sd["s_branch.bias"]).data_ptr()
         st.w_trn, st.b_trn = self._dev(sd["trn_branch.weight"]).data_ptr(), self._dev(sd["trn_branch.bias"]).data_ptr()
         if "nr_branch.weight" in sd:
             st.w_nr = self._dev(sd["nr_branch.weight"]).data_ptr()
@@ -110,13 +142,16 @@ class PreparedPyramid:
         return out, data
 
 
-def warp(levels, x, k0=-8, max_level=None, min_level=0, ms=None):
+def warp(levels, x, k0=-8, max_level=None, min_level=0, ms=None, motion=None, rotation_format=None):
     """levels: NDPLayer modules or their state dicts (level i has m = i + 1
-    unless the module says otherwise or `ms` is given).  For repeated warps
-    with the same weights build a PreparedPyramid once."""
+    unless the module says otherwise or `ms` is given).  `motion` /
+    `rotation_format` name the head of state dicts (default SE3 / axis_angle;
+    modules carry their own).  For repeated warps with the same weights build a
+    PreparedPyramid once."""
     xt = torch.as_tensor(x)
     dev = xt.device if xt.is_cuda else None
-    return PreparedPyramid(levels, k0=k0, ms=ms, device=dev).warp(x, max_level, min_level)
+    return PreparedPyramid(levels, k0=k0, ms=ms, device=dev, motion=motion,
+                           rotation_format=rotation_format).warp(x, max_level, min_level)
 
 
 def warp_pyramid(pyramid, x, max_level=None, min_level=0):

@@ -19,8 +19,10 @@ device) and ``pcr_adam_masked`` (Adam for all tensors of the level, skipped once
 the rule fired) -- captured once per level with torch.cuda.graph and replayed
 ``iters`` times with no host round trip (the reference synchronises on
 ``loss.item()`` every iteration).  The final all-level warp is libpcr's
-pcr_ndp_warp (a10).  Supported: motion "SE3", rotation "axis_angle" (the C5
-configuration, config/NDP.yaml).
+pcr_ndp_warp (a10).  Supported: every head of the reference's NDPLayer --
+``motion_type`` "SE3", "Sim3" or "sflow" with ``rotation_format`` "axis_angle",
+"euler", "quaternion" or "6D" (config/NDP.yaml ships SE3 / axis_angle, the C5
+configuration) -- on the fused kernels and on the torch path alike.
 """
 from __future__ import annotations
 
@@ -36,7 +38,7 @@ import torch.nn.functional as Fn
 
 from . import _lib
 from .chamfer import compute_truncated_chamfer_distance
-from .ndp import warp_pyramid
+from .ndp import MOTIONS, ROT_ROWS, ROTATION_FORMATS, head_code, warp_pyramid
 
 
 @dataclass
@@ -68,7 +70,7 @@ class NDPConfig:
 
 # --------------------------------------------------------------------------
 # mirror of the reference modules (same parameter names: state dicts load
-# into either), nets.py:111-177 and rigid_body.py:89-119
+# into either), nets.py:66-177 and rigid_body.py:5-119
 # --------------------------------------------------------------------------
 
 
@@ -89,17 +91,57 @@ def _skew(w):
                         -w[..., 1], w[..., 0], z], dim=-1).reshape((-1, 3, 3))
 
 
-class NDPLayer(nn.Module):
-    """NDPLayer(depth, width, k0, m, 'axis_angle', nonrigidity_est, 'SE3')."""
+def _euler_to_so3(a):
+    """Rx(a0) Ry(a1) Rz(a2) (rigid_body.euler_to_SO3, convention X, Y, Z)."""
+    c, s = torch.cos(a), torch.sin(a)
+    one, zero = torch.ones_like(a[..., 0]), torch.zeros_like(a[..., 0])
 
-    def __init__(self, depth, width, k0, m, nonrigidity_est=False):
+    def mat(*flat):
+        return torch.stack(flat, dim=-1).reshape(a.shape[:-1] + (3, 3))
+    Rx = mat(one, zero, zero, zero, c[..., 0], -s[..., 0], zero, s[..., 0], c[..., 0])
+    Ry = mat(c[..., 1], zero, s[..., 1], zero, one, zero, -s[..., 1], zero, c[..., 1])
+    Rz = mat(c[..., 2], -s[..., 2], zero, s[..., 2], c[..., 2], zero, zero, zero, one)
+    return torch.matmul(torch.matmul(Rx, Ry), Rz)
+
+
+def _quaternion_to_so3(o):
+    """o / copysign(|o|, o[0]) then rigid_body.quaternion_to_SO3 (nets.py:154-157)."""
+    n = torch.sqrt((o * o).sum(-1))
+    q = o / torch.where(o[..., 0] < 0, -n, n)[..., None]
+    r, i, j, k = torch.unbind(q, -1)
+    two_s = 2.0 / (q * q).sum(-1)
+    flat = (1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
+            two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r),
+            two_s * (i * k - j * r), two_s * (j * k + i * r), 1 - two_s * (i * i + j * j))
+    return torch.stack(flat, -1).reshape(q.shape[:-1] + (3, 3))
+
+
+def _6d_to_so3(d6):
+    """rigid_body._6d_to_SO3: Gram-Schmidt of the two 3-vectors, rows b1, b2, b1 x b2."""
+    a1, a2 = d6[..., :3], d6[..., 3:]
+    b1 = Fn.normalize(a1, dim=-1)
+    b2 = Fn.normalize(a2 - (b1 * a2).sum(-1, keepdim=True) * b1, dim=-1)
+    return torch.stack((b1, b2, torch.cross(b1, b2, dim=-1)), dim=-2)
+
+
+class NDPLayer(nn.Module):
+    """NDPLayer(depth, width, k0, m, rotation_format, nonrigidity_est, motion) of the
+    reference, every head; keyword order differs (rotation_format defaults to
+    "axis_angle", the shipped configuration)."""
+
+    def __init__(self, depth, width, k0, m, nonrigidity_est=False, rotation_format="axis_angle",
+                 motion="SE3"):
         super().__init__()
+        head_code(motion, rotation_format)  # ValueError listing the choices
         self.k0, self.m = k0, m
-        self.motion, self.rotation_format = "SE3", "axis_angle"
+        self.motion, self.rotation_format = motion, rotation_format
         self.nonrigidity_est = nonrigidity_est
         self.input = nn.Sequential(nn.Linear(6, width), nn.ReLU())
         self.mlp = _MLP(depth, width)
-        self.rot_brach = nn.Linear(width, 3)
+        if motion != "sflow":
+            self.rot_brach = nn.Linear(width, ROT_ROWS[rotation_format])
+            if motion == "Sim3":
+                self.s_branch = nn.Linear(width, 1)
         self.trn_branch = nn.Linear(width, 3)
         if nonrigidity_est:
             self.nr_branch = nn.Linear(width, 1)
@@ -117,12 +159,13 @@ class NDPLayer(nn.Module):
     def forward(self, x):
         fea = self.mlp(self.input(self.posenc(x)))
         t = self.mlp_scale * self.trn_branch(fea)
-        r = self.mlp_scale * self.rot_brach(fea)
-        theta = torch.norm(r, dim=-1, keepdim=True)
-        W = _skew(r / theta)
-        th = theta[..., None]
-        R = torch.eye(3, device=x.device)[None] + torch.sin(th) * W + (1 - torch.cos(th)) * W @ W
-        x_ = (R @ x[..., None]).squeeze() + t
+        if self.motion == "sflow":
+            x_ = x + t
+        else:
+            Rx = (self.get_rotation(fea) @ x[..., None]).squeeze()
+            if self.motion == "Sim3":
+                Rx = (self.mlp_scale * self.s_branch(fea) + 1) * Rx  # starts at scale 1
+            x_ = Rx + t
         if self.nonrigidity_est:
             nr = torch.sigmoid(self.mlp_scale * self.nr_branch(fea))
             x_ = x + nr * (x_ - x)
@@ -131,14 +174,29 @@ class NDPLayer(nn.Module):
             nr = None
         return x_.squeeze(), nr
 
+    def get_rotation(self, fea):
+        r = self.mlp_scale * self.rot_brach(fea)
+        if self.rotation_format == "euler":
+            return _euler_to_so3(r)
+        if self.rotation_format == "quaternion":
+            return _quaternion_to_so3(r)
+        if self.rotation_format == "6D":
+            return _6d_to_so3(r)
+        theta = torch.norm(r, dim=-1, keepdim=True)
+        W = _skew(r / theta)
+        th = theta[..., None]
+        return torch.eye(3, device=fea.device)[None] + torch.sin(th) * W + (1 - torch.cos(th)) * W @ W
+
 
 class DeformationPyramid:
-    """Deformation_Pyramid(depth, width, device, k0, m, 'axis_angle',
-    nonrigidity_est, 'SE3') (nets.py:10-65)."""
+    """Deformation_Pyramid(depth, width, device, k0, m, rotation_format,
+    nonrigidity_est, motion) (nets.py:10-65)."""
 
-    def __init__(self, depth, width, device, k0, m, nonrigidity_est=False):
-        self.pyramid = [NDPLayer(depth, width, k0, i + 1, nonrigidity_est and i != 0).to(device)
-                        for i in range(m)]
+    def __init__(self, depth, width, device, k0, m, nonrigidity_est=False, rotation_format="axis_angle",
+                 motion="SE3"):
+        self.motion, self.rotation_format = motion, rotation_format
+        self.pyramid = [NDPLayer(depth, width, k0, i + 1, nonrigidity_est and i != 0, rotation_format,
+                                 motion).to(device) for i in range(m)]
         self.n_hierarchy = m
 
     def warp(self, x, max_level=None, min_level=0):
@@ -296,7 +354,8 @@ class _Level:
 class _NdpLevelC(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("w_in", "b_in", "w_hid", "b_hid", "w_rot", "b_rot",
                                                "w_trn", "b_trn", "w_nr", "b_nr")] + \
-        [("m", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+        [("m", ctypes.c_int32), ("reserved", ctypes.c_int32), ("w_s", ctypes.c_void_p),
+         ("b_s", ctypes.c_void_p), ("head", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
 
 
 class _TrainC(ctypes.Structure):
@@ -354,21 +413,29 @@ class _LevelFused(_Level):
         self.N = N
         self.pe = buf("pe", lambda: torch.zeros(6, N, **f32))
         self.H = buf("H", lambda: torch.zeros(d, W, N, **f32))
-        self.aux = buf("aux", lambda: torch.zeros(8, N, **f32))
-        self.dO = buf("dO", lambda: torch.zeros(8, N, **f32))
+        # the head's row map, from the library (include/pcr_api.h: pcr_ndp_head_rows)
+        self.head = head = head_code(getattr(layer, "motion", "SE3"),
+                                     getattr(layer, "rotation_format", "axis_angle"))
+        lib = _lib.load()
+        rot_n, rows, brows, trn0, nr0, sc0 = (int(lib.pcr_ndp_head_rows(head, k)) for k in range(6))
+        self.nr_row = nr0
+        self.aux = buf(f"aux{rows}", lambda: torch.zeros(rows, N, **f32))
+        self.dO = buf(f"dO{rows}", lambda: torch.zeros(rows, N, **f32))
         self.D = buf("D", lambda: torch.zeros(d, W, N, **f32))
         self.gx = buf("gx", lambda: torch.zeros(N, 3, **f32))
         self.xo = self.warped  # the forward writes the level output in place
-        nparts = _lib.load().pcr_ndp_train_partial_floats(N, W, d, self.CHUNK)
-        self.part = buf("part", lambda: torch.zeros(max(int(nparts), 1), **f32))
+        nparts = lib.pcr_ndp_train_partial_floats_head(N, W, d, self.CHUNK, head)
+        self.part = buf(f"part{brows}", lambda: torch.zeros(max(int(nparts), 1), **f32))
         # gradient buffers in the kernel's order; the Adam table must see the same
         # storage, so the branch parameters' grads are row views of one buffer
-        self.gw_b = buf("gw_b", lambda: torch.zeros(7, W, **f32))
-        self.gb_b = buf("gb_b", lambda: torch.zeros(7, **f32))
+        self.gw_b = buf(f"gw_b{brows}", lambda: torch.zeros(brows, W, **f32))
+        self.gb_b = buf(f"gb_b{brows}", lambda: torch.zeros(brows, **f32))
         names = [n for n, _ in layer.named_parameters()]
-        view = {"rot_brach.weight": self.gw_b[0:3], "rot_brach.bias": self.gb_b[0:3],
-                "trn_branch.weight": self.gw_b[3:6], "trn_branch.bias": self.gb_b[3:6],
-                "nr_branch.weight": self.gw_b[6:7], "nr_branch.bias": self.gb_b[6:7]}
+        view = {"rot_brach.weight": self.gw_b[0:rot_n], "rot_brach.bias": self.gb_b[0:rot_n],
+                "trn_branch.weight": self.gw_b[trn0:trn0 + 3], "trn_branch.bias": self.gb_b[trn0:trn0 + 3],
+                "nr_branch.weight": self.gw_b[nr0:nr0 + 1], "nr_branch.bias": self.gb_b[nr0:nr0 + 1]}
+        if sc0 >= 0:
+            view.update({"s_branch.weight": self.gw_b[sc0:sc0 + 1], "s_branch.bias": self.gb_b[sc0:sc0 + 1]})
         own = {n: buf("g:" + n, lambda p=p: torch.zeros_like(p)) for n, p in layer.named_parameters() if n not in view}
         order = ["input.0.weight", "input.0.bias"]
         for k in range(self.nhid):
@@ -382,7 +449,11 @@ class _LevelFused(_Level):
         t.x, t.N, t.width, t.depth, t.k0 = s_sample.data_ptr(), N, W, d, int(layer.k0)
         lv = _NdpLevelC()
         lv.w_in, lv.b_in = sd["input.0.weight"].data_ptr(), sd["input.0.bias"].data_ptr()
-        lv.w_rot, lv.b_rot = sd["rot_brach.weight"].data_ptr(), sd["rot_brach.bias"].data_ptr()
+        lv.head = head
+        if "rot_brach.weight" in sd:
+            lv.w_rot, lv.b_rot = sd["rot_brach.weight"].data_ptr(), sd["rot_brach.bias"].data_ptr()
+        if "s_branch.weight" in sd:
+            lv.w_s, lv.b_s = sd["s_branch.weight"].data_ptr(), sd["s_branch.bias"].data_ptr()
         lv.w_trn, lv.b_trn = sd["trn_branch.weight"].data_ptr(), sd["trn_branch.bias"].data_ptr()
         self.has_nr = "nr_branch.weight" in sd
         if self.has_nr:
@@ -486,7 +557,7 @@ class _LevelFused(_Level):
             # the Chamfer with its gradient, then the loss and the early-stop rule in one launch
             _lib.call("pcr_ndp_chamfer_step", ctypes.byref(self.nc), st)
             _lib.call("pcr_ndp_chamfer_loss", _lib.ptr(self.d1), self.K, _lib.ptr(self.d2), self.M,
-                      _lib.ptr(self.aux[6] if self.bce_on else None), self.N, float(cfg.w_reg), 1e9,
+                      _lib.ptr(self.aux[self.nr_row] if self.bce_on else None), self.N, float(cfg.w_reg), 1e9,
                       _lib.ptr(self.loss), _lib.ptr(self.log), _lib.ptr(self.ctr), int(cfg.iters),
                       _lib.ptr(self.state), float(cfg.break_threshold_ratio), int(cfg.max_break_count), 1e-4,
                       _lib.ptr(self.loss_scratch), st)
@@ -510,7 +581,7 @@ class _LevelFused(_Level):
         nnd_forward_cuda(xs, self.t3, self.d1, self.d2, self.i1, self.i2)
         # loss (truncated Chamfer means + BCE), dL/dd1, dL/dd2, the log entry, the counter
         _lib.call("pcr_ndp_chamfer_glue", _lib.ptr(self.d1), self.K, _lib.ptr(self.d2), self.M,
-                  _lib.ptr(self.aux[6] if self.bce_on else None), self.N, float(cfg.w_reg), 1e9,
+                  _lib.ptr(self.aux[self.nr_row] if self.bce_on else None), self.N, float(cfg.w_reg), 1e9,
                   _lib.ptr(self.gd1), _lib.ptr(self.gd2), _lib.ptr(self.loss), _lib.ptr(self.log),
                   _lib.ptr(self.ctr), int(cfg.iters), st)
         nnd_backward_cuda(xs, self.t3, self.gsub, self.gt, self.gd1, self.gd2, self.i1, self.i2)
@@ -523,16 +594,20 @@ def optimize_deformation_pyramid(src_pcd, tgt_pcd, inds, config=None, NDP=None, 
                                  fused=True):
     """Returns (warped_pcd (N, 3) cuda f32, hist (levels + 1, N_s, 3) numpy, iter_cnt) like
     the reference, plus ``info`` per level {steps, evaluated, last_loss}.  ``NDP`` may be
-    the reference's Deformation_Pyramid (SE3 / axis_angle) or this module's mirror;
-    by default a fresh mirror is built from the config, as the reference does."""
+    the reference's Deformation_Pyramid (any motion and rotation format; its layers
+    say which) or this module's mirror; by default a fresh mirror is built from the
+    config (``motion_type``, ``rotation_format``), as the reference does."""
     cfg = NDPConfig.from_any(config or {})
-    if cfg.motion_type != "SE3" or cfg.rotation_format != "axis_angle":
-        raise NotImplementedError("f4 implements motion SE3 + axis_angle (config/NDP.yaml)")
+    if cfg.motion_type not in MOTIONS:
+        raise ValueError(f"motion_type {cfg.motion_type!r} not in {MOTIONS}")
+    if cfg.rotation_format not in ROTATION_FORMATS:
+        raise ValueError(f"rotation_format {cfg.rotation_format!r} not in {ROTATION_FORMATS}")
     dev = torch.device("cuda", torch.cuda.current_device())
     src = torch.as_tensor(src_pcd, dtype=torch.float32).to(dev)
     tgt = torch.as_tensor(tgt_pcd, dtype=torch.float32).to(dev)
     if NDP is None:
-        NDP = DeformationPyramid(cfg.depth, cfg.width, dev, cfg.k0, cfg.m, cfg.w_reg > 0)
+        NDP = DeformationPyramid(cfg.depth, cfg.width, dev, cfg.k0, cfg.m, cfg.w_reg > 0,
+                                 cfg.rotation_format, cfg.motion_type)
     src_mean = src.mean(dim=0, keepdim=True)
     tgt_mean = tgt.mean(dim=0, keepdim=True)
     src_c = (src - src_mean).contiguous()
