@@ -569,7 +569,7 @@ int pcr_adam_masked(const pcr_adam_tensor *tensors, int32_t n_tensors, int32_t m
  *   (gate = the level's state, a device pointer), every kernel that
  *   pcr_nnd_forward / pcr_nnd_backward / pcr_ndp_train_forward /
  *   pcr_ndp_train_backward / pcr_ndp_chamfer_glue / pcr_ndp_chamfer_step /
- *   pcr_ndp_chamfer_loss launch reads gate[0] at entry
+ *   pcr_ndp_chamfer_loss / pcr_ndp_ldmk_loss launch reads gate[0] at entry
  *   and returns at once when it is 0 -- so the replays of a captured level graph
  *   left after the rule fired cost only their launches.  pcr_set_gate(NULL)
  *   restores ungated launches.  Thread-local; captured launches keep the pointer
@@ -623,6 +623,18 @@ typedef struct pcr_ndp_train {
      * gsub; K = gacc_k */
     const long long *gacc;
     int32_t gacc_k, reserved;
+    /* optional landmark block (null = off; registration.py:213-227): the first
+     * ldmk_n points of x are landmarks with targets ldmk_tgt (ldmk_n,3).  The
+     * backward gives them dL/dx_out[p][c] = f32(2 / ldmk_n) * (x_out[p][c] -
+     * ldmk_tgt[p][c]), read from x_out (the gradient of mean_k sum_c (x_out -
+     * ldmk_tgt)^2; no gradient buffer), whatever inv / g say about them, and
+     * multiplies the gradient of every other point (gacc or gsub through inv, or
+     * g) once by f32(cd_scale).  inv and g may both be null (every gradient is
+     * the landmarks').  1 <= ldmk_n <= N, else PCR_ERR_ARG.  The forward does not
+     * read the block: landmarks and samples are rows of one (N,3) input. */
+    const float *ldmk_tgt;
+    int32_t ldmk_n, reserved3;
+    double cd_scale;
 } pcr_ndp_train;
 int pcr_ndp_train_forward(const pcr_ndp_train *t, pcr_stream_t stream);
 int pcr_ndp_train_backward(const pcr_ndp_train *t, float *part, int32_t chunk,
@@ -681,6 +693,23 @@ int pcr_ndp_chamfer_loss(const float *d1, int32_t K, const float *d2, int32_t M,
                          int32_t N, double w_reg, double trunc, float *loss, float *log, int64_t *ctr,
                          int32_t log_last, double *state, double break_threshold_ratio,
                          int32_t max_break_count, double stop_loss, void *scratch, pcr_stream_t stream);
+/* pcr_ndp_ldmk_loss: pcr_ndp_chamfer_loss with the landmark term of
+ *   registration.py:213-227 in front:
+ *   loss = mean_k sum_c (x_out[k][c] - ldmk_tgt[k][c])^2 over the L landmarks (the
+ *   first L rows of x_out) + f32(w_cd) * (sum(d1')/K + sum(d2')/M)
+ *   [+ f32(w_reg) * mean(-max(log(1 - s), -100)) over the P entries of s], the
+ *   same fixed reduction (32 workgroups, partials summed in block order), log
+ *   entry, counter and -- when state is given -- early-stop rule, in one launch.
+ *   K = M = 0 (d1, d2 may be null) is the landmark-only loss (w_cd <= 0 in the
+ *   reference): no Chamfer part.  L >= 1; K and M both 0 or both >= 1; else
+ *   PCR_ERR_ARG and nothing is written.  scratch:
+ *   pcr_ndp_ldmk_loss_scratch_bytes() bytes, zeroed once by the caller. */
+int64_t pcr_ndp_ldmk_loss_scratch_bytes(void);
+int pcr_ndp_ldmk_loss(const float *x_out, const float *ldmk_tgt, int32_t L, const float *d1, int32_t K,
+                      const float *d2, int32_t M, const float *s, int32_t P, double w_cd, double w_reg,
+                      double trunc, float *loss, float *log, int64_t *ctr, int32_t log_last, double *state,
+                      double break_threshold_ratio, int32_t max_break_count, double stop_loss, void *scratch,
+                      pcr_stream_t stream);
 #define PCR_NDP_GACC_REPLICAS 16
 typedef struct pcr_ndp_chamfer {
     const float *xs;

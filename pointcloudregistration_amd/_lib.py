@@ -127,6 +127,8 @@ SIGNATURES = {
     "pcr_ndp_chamfer_step": [_p, _p],
     "pcr_ndp_chamfer_loss": [_p, _i32, _p, _i32, _p, _i32, _f64, _f64, _p, _p, _p, _i32, _p, _f64, _i32,
                              _f64, _p, _p],
+    "pcr_ndp_ldmk_loss": [_p, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _f64, _f64, _f64, _p, _p, _p, _i32, _p,
+                          _f64, _i32, _f64, _p, _p],
     "pcr_pipeline_step": [_p, _p, _p, _p],
     "pcr_pipeline_records": [_p, _p],
     "pcr_hybrid_search": [_p, _i32, _i32, _p, _f64, _i32, _p, _p, _p, _p],
@@ -201,6 +203,8 @@ def load():
         lib.pcr_ndp_chamfer_scratch_bytes.argtypes = [_i32, _i32]
         lib.pcr_ndp_loss_scratch_bytes.restype = _i64
         lib.pcr_ndp_loss_scratch_bytes.argtypes = []
+        lib.pcr_ndp_ldmk_loss_scratch_bytes.restype = _i64
+        lib.pcr_ndp_ldmk_loss_scratch_bytes.argtypes = []
         lib.pcr_ndp_chamfer_gacc_words.restype = _i64
         lib.pcr_ndp_chamfer_gacc_words.argtypes = [_i32]
         lib.pcr_ndp_chamfer_max_points.restype = _i32
@@ -241,7 +245,8 @@ def exported_symbols():
     return ["pcr_last_error", "pcr_version", "pcr_workspace_release", "pcr_profile_enable", "pcr_profile_read",
             "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_featnn_image_chunks", "pcr_ndp_train_partial_floats", "pcr_ndp_train_partial_floats_head", "pcr_ndp_head_rows",
             "pcr_ndp_chamfer_scratch_bytes",
-            "pcr_ndp_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words", "pcr_ndp_chamfer_max_points",
+            "pcr_ndp_loss_scratch_bytes", "pcr_ndp_ldmk_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words",
+            "pcr_ndp_chamfer_max_points",
             "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_attention_scratch_bytes",
             "pcr_offset_attention_scratch_bytes", "pcr_pointnet_scratch_bytes", "pcr_edge_conv_scratch_bytes",
             "pcr_group_mlp_scratch_bytes", "pcr_unary_scratch_bytes", "pcr_pointwise_scratch_bytes",

@@ -124,14 +124,25 @@ def execute_global_registration(source, target, source_feats, target_feats, voxe
 
 
 def register_c2p(source, target, source_feats, target_feats, voxel_size, dist_thresh=None,
-                 ndp_config=None, NDP=None, seed=0, pair_id=0, use_graph=True):
+                 ndp_config=None, NDP=None, seed=0, pair_id=0, use_graph=True, landmarks=None):
     """testScript.py:161-196 on the device: vote -> RANSAC (distance dist_thresh,
     default voxel_size: dist_thresh_maps['10000'] = first_subsampling_dl) ->
     estimate = T source (f64, then f32 as the reference's .float()) -> NDP
     optimisation on the unique inlier source indices.  Returns a dict with
     T (4,4) f64, warped (n,3) f32 cuda, corrs (K,) int64, the RANSAC result
-    fields and the NDP per-level info."""
+    fields, the NDP per-level info and the landmarks the NDP stage was given.
+
+    ``landmarks`` selects the landmark branch of the NDP optimisation
+    (ndp_opt.optimize_deformation_pyramid, config/LNDP.yaml; ``w_cd`` and
+    ``trunc_cd`` of ``ndp_config`` are read then): None -- as above; a pair
+    (src_ldmk (L,3), tgt_ldmk (L,3)) -- passed through, the source landmarks taken
+    in the frame of ``estimate``; "ransac" -- the inlier correspondences this call
+    already holds, (estimate[corrs], target[corr_tgt[corrs]]).  The reference's
+    LNDP takes its landmarks from Lepard's matches (with its outlier rejection),
+    which stays out of scope here."""
     from .ndp_opt import optimize_deformation_pyramid
+    if isinstance(landmarks, str) and landmarks != "ransac":
+        raise ValueError(f"landmarks {landmarks!r}: None, \"ransac\" or a pair of (L,3) arrays")
     dev = _device()
     src = _cuda(source, torch.float32, dev).reshape(-1, 3)
     tgt = _cuda(target, torch.float32, dev).reshape(-1, 3)
@@ -146,10 +157,14 @@ def register_c2p(source, target, source_feats, target_feats, voxel_size, dist_th
     est = transform_batch(src.unsqueeze(0), br.transformation)[0]
     ct = br.corr_tgt[0]
     corrs = torch.nonzero(ct >= 0).flatten()  # ascending = np.unique of the set's sources
+    if isinstance(landmarks, str):
+        landmarks = (est[corrs], tgt[ct[corrs].long()])
     warped, hist, _, info = optimize_deformation_pyramid(est, tgt, corrs.cpu().numpy(),
-                                                         ndp_config, NDP, use_graph=use_graph)
+                                                         ndp_config, NDP, use_graph=use_graph,
+                                                         landmarks=landmarks)
     return {"T": br.transformation[0], "fitness": br.fitness[0], "inlier_rmse": br.inlier_rmse[0],
             "estimate": est, "corrs": corrs, "warped": warped, "hist": hist, "info": info,
+            "landmarks": landmarks,
             "source_feats_h": fs_h, "target_feats_h": ft_h}
 
 

@@ -9,7 +9,11 @@
 // (nets.py:111-140, motion SE3, rotation axis_angle, rigid_body.py:89-119) in
 // f32, its gradient by the chain rule written out below, nn.Linear weight
 // gradients dW = sum_p delta_p (x) a_p, bias gradients sum_p delta_p, and the
-// loss of :231-244 (truncated Chamfer means + w_reg * mean BCE(s, 0)).
+// loss of :231-244 (truncated Chamfer means + w_reg * mean BCE(s, 0)).  The
+// landmark branch of the same loop (:213-227) is a block of ndp_train_bwd (the
+// first ldmk_n points take the landmark term's gradient from x_out) and
+// ndp_loss_kernel<true> (pcr_ndp_ldmk_loss: the landmark mean in front of the
+// w_cd-weighted Chamfer part).
 //
 // Layouts (N points of the level):
 //   activations H_l, deltas D_l, positional encoding, branch data: FEATURE-major
@@ -74,6 +78,13 @@ struct TrainArgs {
     const float *gsub;
     const long long *gacc;          // or: the subset gradient in 2^-44 fixed point (ndp_chamfer.hip)
     int gacc_k;                     // its K (replica stride)
+    // landmark block (optional, registration.py:213-227): points p < ldmk_n are
+    // landmarks, dL/dx'[p] = ldmk_scale (x_out[p] - ldmk_tgt[p]) with ldmk_scale =
+    // f32(2 / ldmk_n) (the gradient of mean_k sum_c (x' - tgt)^2); the other
+    // points' gradient (gacc / gsub through inv, or g) is multiplied by cd_scale
+    const float *ldmk_tgt;
+    int ldmk_n;
+    float ldmk_scale, cd_scale;
     const double *gate;             // f4 early stop (pcr_internal.h), or null
 };
 
@@ -193,11 +204,12 @@ __global__ __launch_bounds__(64 * kNT) void ndp_train_bwd(TrainArgs a) {
     if (w == 0) {
         const float x[3] = {valid ? a.x[3 * pt] : 0.f, valid ? a.x[3 * pt + 1] : 0.f, valid ? a.x[3 * pt + 2] : 0.f};
         float g[3] = {0.f, 0.f, 0.f};
+        const bool is_ldmk = a.ldmk_tgt && pt < a.ldmk_n;  // ldmk_n <= N: a valid point
         if (a.inv && a.gacc) {
             // the two-word fixed point of ndp_chamfer.hip: header word = flag bit 0,
             // (s + 2048) << 8; hi words at 2^-s, lo words (after all hi) at 2^-(s+40);
             // half h sums replicas h, h + 2, ... (integer sums: exact, any order)
-            const int k = valid ? a.inv[pt] : -1;
+            const int k = valid && !is_ldmk ? a.inv[pt] : -1;
             const long long hw = a.gacc[0];
             const float bad = (hw & 1) ? __builtin_nanf("") : 0.0f;
             int sh = (int)(hw >> 8) - 2048;
@@ -218,14 +230,19 @@ __global__ __launch_bounds__(64 * kNT) void ndp_train_bwd(TrainArgs a) {
                 const double v = __builtin_ldexp((double)vh, -sh) + __builtin_ldexp((double)vl, -sh - 40);
                 g[c] = k >= 0 ? (float)v + bad : 0.0f;
             }
-        } else if (!valid) {
+        } else if (!valid || is_ldmk) {
         } else if (a.inv) {
             const int k = a.inv[pt];
             g[0] = k >= 0 ? a.gsub[3 * k] : 0.0f;
             g[1] = k >= 0 ? a.gsub[3 * k + 1] : 0.0f;
             g[2] = k >= 0 ? a.gsub[3 * k + 2] : 0.0f;
-        } else {
+        } else if (a.g) {
             g[0] = a.g[3 * pt]; g[1] = a.g[3 * pt + 1]; g[2] = a.g[3 * pt + 2];
+        }
+        if (a.ldmk_tgt) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                g[c] = is_ldmk ? a.ldmk_scale * (a.x_out[3 * pt + c] - a.ldmk_tgt[3 * pt + c]) : g[c] * a.cd_scale;
         }
         float aux[M.n];
 #pragma unroll
@@ -484,10 +501,16 @@ struct LossArgs {
     double *state;  // or null (no rule)
     double ratio, stop_loss;
     int max_break;
-    float *part;    // [3][kLossBlocks]
+    float *part;    // [3][kLossBlocks], with the landmark part [4][kLossBlocks]
     unsigned *done; // zero between launches (the last block resets it)
+    // LDMK (pcr_ndp_ldmk_loss): the landmark part mean_k sum_c (xl[k][c] - tl[k][c])^2
+    // in front, the Chamfer part times w_cd (absent when g.K == 0: mode B)
+    const float *xl, *tl;
+    int L;
+    float w_cd;
 };
 
+template <bool LDMK>
 __global__ __launch_bounds__(256) void ndp_loss_kernel(LossArgs a) {
     const GlueArgs &g = a.g;
     if (gated_off(g.gate)) return;
@@ -499,8 +522,22 @@ __global__ __launch_bounds__(256) void ndp_loss_kernel(LossArgs a) {
         lo = min(n, b * per);
         hi = min(n, lo + per);
     };
-    float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+    float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f, s0 = 0.0f;
     int lo, hi;
+    if constexpr (LDMK) {
+        __shared__ float red0[4];
+        range(a.L, lo, hi);
+        for (int i = lo + t; i < hi; i += 256) {
+            const float e0 = a.xl[3 * i] - a.tl[3 * i], e1 = a.xl[3 * i + 1] - a.tl[3 * i + 1],
+                        e2 = a.xl[3 * i + 2] - a.tl[3 * i + 2];
+            s0 += (e0 * e0 + e1 * e1) + e2 * e2;
+        }
+#pragma unroll
+        for (int o = 32; o; o >>= 1) s0 += __shfl_xor(s0, o, 64);
+        if (lane == 0) red0[wv] = s0;
+        __syncthreads();
+        if (t == 0) a.part[3 * kLossBlocks + b] = ((red0[0] + red0[1]) + red0[2]) + red0[3];
+    }
     range(g.K, lo, hi);
     for (int i = lo + t; i < hi; i += 256) {
         const float d = g.d1[i];
@@ -542,7 +579,16 @@ __global__ __launch_bounds__(256) void ndp_loss_kernel(LossArgs a) {
         S2 += __hip_atomic_load(a.part + kLossBlocks + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         S3 += __hip_atomic_load(a.part + 2 * kLossBlocks + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    float L = S1 / (float)g.K + S2 / (float)g.M;
+    float L;
+    if constexpr (LDMK) {
+        float S0 = 0.0f;
+        for (int k = 0; k < kLossBlocks; ++k)
+            S0 += __hip_atomic_load(a.part + 3 * kLossBlocks + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        L = S0 / (float)a.L;
+        if (g.K > 0) L = L + a.w_cd * (S1 / (float)g.K + S2 / (float)g.M);
+    } else {
+        L = S1 / (float)g.K + S2 / (float)g.M;
+    }
     if (g.s) L = L + g.w_reg * (-S3 / (float)g.N);
     *g.loss = L;
     const long long c = *g.ctr;
@@ -584,6 +630,12 @@ static int fill_train(const pcr_ndp_train *t, pcr::TrainArgs &a) {
     a.pe = t->pe; a.H = t->H; a.aux = t->aux; a.x_out = t->x_out;
     a.g = t->g; a.bce_scale = t->bce_scale; a.dO = t->dO; a.D = t->D;
     a.inv = t->inv; a.xs = t->xs; a.gsub = t->gsub; a.gacc = t->gacc; a.gacc_k = t->gacc_k;
+    if (t->ldmk_tgt) {
+        PCR_REQUIRE(t->ldmk_n >= 1 && t->ldmk_n <= t->N, PCR_ERR_ARG, "ndp_train: ldmk_n %d of N %d", t->ldmk_n, t->N);
+        a.ldmk_tgt = t->ldmk_tgt; a.ldmk_n = t->ldmk_n;
+        a.ldmk_scale = (float)(2.0 / (double)t->ldmk_n);
+        a.cd_scale = (float)t->cd_scale;
+    }
     a.gate = pcr::current_gate();
     return PCR_OK;
 }
@@ -617,7 +669,8 @@ extern "C" int pcr_ndp_train_backward(const pcr_ndp_train *t, float *part, int32
     int rc = fill_train(t, a);
     if (rc != PCR_OK) return rc;
     if (a.N == 0) return PCR_OK;
-    PCR_REQUIRE((a.inv ? (a.gsub != nullptr || a.gacc != nullptr) : a.g != nullptr) && a.dO && a.D && part && grads, PCR_ERR_ARG,
+    PCR_REQUIRE((a.inv ? (a.gsub != nullptr || a.gacc != nullptr) : (a.g != nullptr || a.ldmk_tgt != nullptr)) && a.dO &&
+                    a.D && part && grads && (!a.ldmk_tgt || a.x_out), PCR_ERR_ARG,
                 "ndp_train_backward: null buffer");
     PCR_REQUIRE(chunk >= 64 && chunk % 64 == 0, PCR_ERR_ARG, "ndp_train_backward: chunk %d", chunk);
     hipStream_t s = pcr::as_stream(stream);
@@ -715,7 +768,7 @@ extern "C" int pcr_ndp_chamfer_loss(const float *d1, int32_t K, const float *d2,
     pcr::clear_error();
     PCR_REQUIRE(K >= 1 && M >= 1 && N >= 0 && log_last >= 0, PCR_ERR_ARG, "ndp_chamfer_loss: bad size");
     PCR_REQUIRE(d1 && d2 && loss && log && ctr && scratch, PCR_ERR_ARG, "ndp_chamfer_loss: null buffer");
-    pcr::LossArgs a;
+    pcr::LossArgs a{};
     a.g = pcr::GlueArgs{d1, d2, s, K, M, N, log_last, (float)trunc, (float)w_reg,
                         (float)(1.0 / (double)K), (float)(1.0 / (double)M), nullptr, nullptr, loss, log,
                         (long long *)ctr};
@@ -726,7 +779,37 @@ extern "C" int pcr_ndp_chamfer_loss(const float *d1, int32_t K, const float *d2,
     a.max_break = max_break_count;
     a.part = (float *)scratch;
     a.done = (unsigned *)(a.part + 3 * pcr::kLossBlocks);
-    hipLaunchKernelGGL(pcr::ndp_loss_kernel, dim3(pcr::kLossBlocks), dim3(256), 0, pcr::as_stream(stream), a);
+    hipLaunchKernelGGL(pcr::ndp_loss_kernel<false>, dim3(pcr::kLossBlocks), dim3(256), 0, pcr::as_stream(stream), a);
+    PCR_LAUNCH_CHECK();
+    return PCR_OK;
+}
+
+extern "C" int64_t pcr_ndp_ldmk_loss_scratch_bytes(void) {
+    return (int64_t)(sizeof(float) * 4 * pcr::kLossBlocks + 64);
+}
+
+extern "C" int pcr_ndp_ldmk_loss(const float *x_out, const float *ldmk_tgt, int32_t L, const float *d1, int32_t K,
+                                 const float *d2, int32_t M, const float *s, int32_t P, double w_cd, double w_reg,
+                                 double trunc, float *loss, float *log, int64_t *ctr, int32_t log_last,
+                                 double *state, double break_threshold_ratio, int32_t max_break_count,
+                                 double stop_loss, void *scratch, pcr_stream_t stream) {
+    pcr::clear_error();
+    PCR_REQUIRE(L >= 1 && P >= 0 && log_last >= 0 && ((K == 0 && M == 0) || (K >= 1 && M >= 1)), PCR_ERR_ARG,
+                "ndp_ldmk_loss: bad size (L %d, K %d, M %d, P %d)", L, K, M, P);
+    PCR_REQUIRE(x_out && ldmk_tgt && (K == 0 || (d1 && d2)) && loss && log && ctr && scratch, PCR_ERR_ARG,
+                "ndp_ldmk_loss: null buffer");
+    pcr::LossArgs a{};
+    a.g = pcr::GlueArgs{d1, d2, s, K, M, P, log_last, (float)trunc, (float)w_reg, 0.0f, 0.0f, nullptr, nullptr,
+                        loss, log, (long long *)ctr};
+    a.g.gate = pcr::current_gate();
+    a.state = state;
+    a.ratio = break_threshold_ratio;
+    a.stop_loss = stop_loss;
+    a.max_break = max_break_count;
+    a.part = (float *)scratch;
+    a.done = (unsigned *)(a.part + 4 * pcr::kLossBlocks);
+    a.xl = x_out; a.tl = ldmk_tgt; a.L = L; a.w_cd = (float)w_cd;
+    hipLaunchKernelGGL(pcr::ndp_loss_kernel<true>, dim3(pcr::kLossBlocks), dim3(256), 0, pcr::as_stream(stream), a);
     PCR_LAUNCH_CHECK();
     return PCR_OK;
 }

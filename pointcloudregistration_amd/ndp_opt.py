@@ -1,8 +1,9 @@
 """f4: the NDP level optimisation as one captured HIP graph per level.
 
-``optimize_deformation_pyramid(src_pcd, tgt_pcd, inds, config)`` is
-Registration.optimize_deformation_pyramid (c2p-net/deformationpyramid/model/
-registration.py:149-289, the no-landmark path the C2P pipeline runs):
+``optimize_deformation_pyramid(src_pcd, tgt_pcd, inds, config, landmarks=None)``
+is Registration.optimize_deformation_pyramid (c2p-net/deformationpyramid/model/
+registration.py:149-289), both branches.  Without landmarks (the path the C2P
+pipeline runs):
 
   * centre both clouds (:171-174);
   * for each level: Adam(lr) on that level's parameters only, up to ``iters``
@@ -23,6 +24,26 @@ pcr_ndp_warp (a10).  Supported: every head of the reference's NDPLayer --
 ``motion_type`` "SE3", "Sim3" or "sflow" with ``rotation_format`` "axis_angle",
 "euler", "quaternion" or "6D" (config/NDP.yaml ships SE3 / axis_angle, the C5
 configuration) -- on the fused kernels and on the torch path alike.
+
+With ``landmarks = (src_ldmk (L, 3), tgt_ldmk (L, 3))`` (the branch
+config/LNDP.yaml and Registration.load_pcds(..., landmarks=...) drive, :185-227,
+266-273): the landmarks are centred by the means of the whole clouds; mode A
+(``w_cd > 0``) warps cat([src_ldmk, s_sample]) each iteration, loss =
+mean_k sum_c (warped_ldmk - tgt_ldmk)^2 + w_cd * Chamfer of all warped samples
+truncated at ``trunc_cd``; mode B (``w_cd <= 0``) warps the landmarks alone, loss =
+the landmark term; the BCE regulariser's mean runs over the warped points (L + N
+or L); the warped landmarks feed the next level in both modes, the warped samples
+in mode A only.  ``w_ldmk`` is in the yaml and never read by the reference, nor
+here.  On the fused path the landmark rows ride in front of the samples in one
+(L + N, 3) level input, the backward takes their gradient f32(2 / L) (x' - tgt)
+from the level output (the landmark block of pcr_ndp_train) and
+``pcr_ndp_ldmk_loss`` makes the loss and applies the early-stop rule; the level
+graph stays one linear chain.  ``hist`` in mode B holds the final warp only,
+(1, N, 3): the reference raises NameError where it records a level there
+(:264, ``s_sample_warped`` is never bound), so there is nothing to match.
+Measured on one MI355X (N = M = 20,000, L = 1,000, 9 levels x 40 iterations):
+mode A replays in 1.015 x the time of the no-landmark loop on all N points, the
+torch path in 12.6 x ("Landmark-guided optimisation").
 """
 from __future__ import annotations
 
@@ -55,6 +76,9 @@ class NDPConfig:
     width: int = 128
     motion_type: str = "SE3"
     rotation_format: str = "axis_angle"
+    # config/LNDP.yaml:16,19 -- read only when landmarks are given
+    w_cd: float = 0.0
+    trunc_cd: float = 0.25
 
     @classmethod
     def from_any(cls, cfg):
@@ -234,8 +258,12 @@ class _Level:
     # a gap of ~8 us on the device; more steps per graph cost capture time
     GRAPH_STEPS = int(os.environ.get("PCR_NDP_GRAPH_STEPS", "2"))
 
-    def __init__(self, layer, s_sample, t_sample, inds, level, cfg: NDPConfig, shared=None):
+    def __init__(self, layer, s_sample, t_sample, inds, level, cfg: NDPConfig, shared=None, ldmk=None):
         dev = s_sample.device
+        # landmark mode (registration.py:211-227): ldmk = (L, tgt_ldmk (L, 3), "A" | "B");
+        # s_sample is then the level's whole input, cat([src_ldmk, samples]) in mode A
+        # and src_ldmk alone in mode B, and inds is not used
+        self.ldmk = ldmk
         # buffers that do not depend on the level (same N, K, M on every level of a
         # pyramid) are allocated once per optimize_deformation_pyramid call
         self.shared = {} if shared is None else shared
@@ -275,7 +303,15 @@ class _Level:
     def step(self):
         cfg = self.cfg
         warped, nr = self.layer(self.s)
-        loss = compute_truncated_chamfer_distance(warped[None, self.inds], self.t[None], trunc=1e9)
+        if self.ldmk is None:
+            loss = compute_truncated_chamfer_distance(warped[None, self.inds], self.t[None], trunc=1e9)
+        else:
+            L, tgt_ldmk, mode = self.ldmk
+            warped = warped.reshape(-1, 3)  # the layer squeezes a single point to (3,)
+            loss = torch.mean(torch.sum((warped[:L] - tgt_ldmk) ** 2, dim=-1))
+            if mode == "A":
+                loss = loss + cfg.w_cd * compute_truncated_chamfer_distance(
+                    warped[None, L:], self.t[None], trunc=cfg.trunc_cd)
         if self.level > 0 and cfg.w_reg > 0:
             loss = loss + cfg.w_reg * _bce_to_zero(nr)
         grads = torch.autograd.grad(loss, self.params)
@@ -367,7 +403,9 @@ class _TrainC(ctypes.Structure):
                 ("x_out", ctypes.c_void_p), ("g", ctypes.c_void_p), ("bce_scale", ctypes.c_double),
                 ("dO", ctypes.c_void_p), ("D", ctypes.c_void_p),
                 ("inv", ctypes.c_void_p), ("xs", ctypes.c_void_p), ("gsub", ctypes.c_void_p),
-                ("gacc", ctypes.c_void_p), ("gacc_k", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("gacc", ctypes.c_void_p), ("gacc_k", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("ldmk_tgt", ctypes.c_void_p), ("ldmk_n", ctypes.c_int32), ("reserved3", ctypes.c_int32),
+                ("cd_scale", ctypes.c_double)]
 
 GACC_REPLICAS = 16  # PCR_NDP_GACC_REPLICAS (include/pcr_api.h)
 
@@ -388,19 +426,23 @@ class _LevelFused(_Level):
     # points per weight-gradient partial (split-K chunk; PCR_NDP_CHUNK: a tuning hook)
     CHUNK = int(os.environ.get("PCR_NDP_CHUNK", "128"))
 
-    def __init__(self, layer, s_sample, t_sample, inds, level, cfg: NDPConfig, shared=None):
+    def __init__(self, layer, s_sample, t_sample, inds, level, cfg: NDPConfig, shared=None, ldmk=None):
         sd = dict(layer.named_parameters())
         self.W = sd["input.0.weight"].shape[0]
         self.nhid = sum(1 for k in sd if k.startswith("mlp.pts_linears.") and k.endswith(".weight"))
         if self.W != 128 or self.nhid > 4:
             raise NotImplementedError("fused NDP training: width 128, depth <= 5")
-        super().__init__(layer, s_sample, t_sample, inds, level, cfg, shared)
+        super().__init__(layer, s_sample, t_sample, inds, level, cfg, shared, ldmk)
         dev, N, W, d = s_sample.device, s_sample.shape[0], self.W, self.nhid + 1
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
+        # landmark mode: N = L + K points in mode A (the K samples are the Chamfer
+        # subset, all of them), N = L in mode B (K = 0: no Chamfer pass)
+        L, mode = (ldmk[0], ldmk[2]) if ldmk is not None else (0, None)
+        K = inds.shape[0] if ldmk is None else N - L
         # the scratch of the kernels depends on (N, W, depth, K, M) only: shared by
         # the levels of one pyramid (keyed by those sizes)
-        key = (N, W, d, inds.shape[0], t_sample.shape[0], t_sample.data_ptr(), inds.data_ptr())
+        key = (N, W, d, K, t_sample.shape[0], t_sample.data_ptr(), inds.data_ptr() if ldmk is None else -L)
 
         def buf(name, make):
             k = (name,) + key
@@ -469,8 +511,22 @@ class _LevelFused(_Level):
         self.bce_on = level > 0 and cfg.w_reg > 0 and self.has_nr
         t.bce_scale = (cfg.w_reg / N) if self.bce_on else 0.0
         t.dO, t.D = self.dO.data_ptr(), self.D.data_ptr()
-        K, M = inds.shape[0], t_sample.shape[0]
+        M = t_sample.shape[0]
         self.K, self.M = K, M
+        if ldmk is not None:
+            self.ldmk_tgt = ldmk[1].contiguous()
+            t.ldmk_tgt, t.ldmk_n, t.cd_scale = self.ldmk_tgt.data_ptr(), L, float(cfg.w_cd)
+            self.ldmk_scratch = buf("ldmk_scratch", lambda: torch.zeros(
+                int(lib.pcr_ndp_ldmk_loss_scratch_bytes()), dtype=torch.uint8, device=dev))
+            # the glue of the nnd path writes a loss of its own: kept out of the level's log
+            self.glue_sink = buf("glue_sink", lambda: (torch.zeros(2, **f32), torch.zeros(1, dtype=torch.long,
+                                                                                         device=dev)))
+        if mode == "B":
+            # every point is a landmark: no subset, no Chamfer pass, no dL/dx' buffer
+            t.g = None
+            self.use_inv = self.use_nc = False
+            self.desc = t
+            return
         self.d1 = buf("d1", lambda: torch.zeros(1, K, **f32))
         self.d2 = buf("d2", lambda: torch.zeros(1, M, **f32))
         self.gd1 = buf("gd1", lambda: torch.zeros(1, K, **f32))
@@ -484,11 +540,14 @@ class _LevelFused(_Level):
         self.t3 = buf("t3", lambda: t_sample[None].contiguous())
         # duplicate-free subset: the forward writes x'[inds] and the backward reads
         # dL/dx' of the subset through inv (no gather / index_add launches)
-        self.use_inv = buf("use_inv", lambda: int(torch.unique(inds).numel()) == K)
+        self.use_inv = mode == "A" or buf("use_inv", lambda: int(torch.unique(inds).numel()) == K)
         if self.use_inv:
             def make_inv():
                 inv = torch.full((N,), -1, **i32)
-                inv[inds] = torch.arange(K, **i32)
+                if mode == "A":  # inv[p] = p - L: xs is the (K, 3) block of samples
+                    inv[L:] = torch.arange(K, **i32)
+                else:
+                    inv[inds] = torch.arange(K, **i32)
                 return inv
             self.inv = buf("inv", make_inv)
             self.xs = buf("xs", lambda: torch.zeros(1, K, 3, **f32))
@@ -510,7 +569,8 @@ class _LevelFused(_Level):
             self.gacc = buf("gacc", lambda: torch.zeros(int(lib.pcr_ndp_chamfer_gacc_words(K)), dtype=torch.int64,
                                                         device=dev))
             c = _ChamferC()
-            c.xs, c.tgt, c.K, c.M, c.trunc = self.xs.data_ptr(), self.t3.data_ptr(), K, M, 1e9
+            c.xs, c.tgt, c.K, c.M = self.xs.data_ptr(), self.t3.data_ptr(), K, M
+            c.trunc = 1e9 if ldmk is None else float(cfg.trunc_cd)
             c.d1, c.d2, c.i1, c.i2 = (self.d1.data_ptr(), self.d2.data_ptr(), self.i1.data_ptr(),
                                       self.i2.data_ptr())
             c.gacc, c.scratch = self.gacc.data_ptr(), self.nc_raw.data_ptr() + off
@@ -518,7 +578,7 @@ class _LevelFused(_Level):
             t.gacc, t.gacc_k = self.gacc.data_ptr(), K
             self.loss_scratch = buf("loss_scratch", lambda: torch.zeros(int(lib.pcr_ndp_loss_scratch_bytes()),
                                                                        dtype=torch.uint8, device=dev))
-            self.xs0 = s_sample.index_select(0, inds).contiguous()
+            self.xs0 = (s_sample.index_select(0, inds) if ldmk is None else s_sample[L:]).contiguous()
             _lib.call("pcr_ndp_chamfer_prepare", ctypes.byref(c), _lib.ptr(self.xs0),
                       _lib.stream_handle(dev))
         self.desc = t
@@ -553,7 +613,25 @@ class _LevelFused(_Level):
         st = _lib.stream_handle(self.s.device)
         desc = ctypes.byref(self.desc)
         _lib.call("pcr_ndp_train_forward", desc, st)
-        if self.use_nc:
+        if self.ldmk is not None:
+            # mode A: the Chamfer of all K samples with its gradient (fused pass, or
+            # the nnd kernels above its size limit); then landmark term + w_cd Chamfer
+            # [+ BCE over all N points] and the early-stop rule in one launch
+            L, mode_a = self.ldmk[0], self.ldmk[2] == "A"
+            if mode_a and self.use_nc:
+                _lib.call("pcr_ndp_chamfer_step", ctypes.byref(self.nc), st)
+            elif mode_a:
+                self._chamfer_nnd(st)
+            _lib.call("pcr_ndp_ldmk_loss", _lib.ptr(self.xo), _lib.ptr(self.ldmk_tgt), L,
+                      _lib.ptr(self.d1 if mode_a else None), self.K if mode_a else 0,
+                      _lib.ptr(self.d2 if mode_a else None), self.M if mode_a else 0,
+                      _lib.ptr(self.aux[self.nr_row] if self.bce_on else None), self.N, float(cfg.w_cd),
+                      float(cfg.w_reg), float(cfg.trunc_cd), _lib.ptr(self.loss), _lib.ptr(self.log),
+                      _lib.ptr(self.ctr), int(cfg.iters), _lib.ptr(self.state), float(cfg.break_threshold_ratio),
+                      int(cfg.max_break_count), 1e-4, _lib.ptr(self.ldmk_scratch), st)
+            _lib.call("pcr_ndp_train_backward", desc, _lib.ptr(self.part), self.CHUNK,
+                      ctypes.cast(self.grad_ptrs, ctypes.c_void_p), st)
+        elif self.use_nc:
             # the Chamfer with its gradient, then the loss and the early-stop rule in one launch
             _lib.call("pcr_ndp_chamfer_step", ctypes.byref(self.nc), st)
             _lib.call("pcr_ndp_chamfer_loss", _lib.ptr(self.d1), self.K, _lib.ptr(self.d2), self.M,
@@ -579,25 +657,65 @@ class _LevelFused(_Level):
         cfg = self.cfg
         xs = self.xs if self.use_inv else self.xo.index_select(0, self.inds)[None].contiguous()
         nnd_forward_cuda(xs, self.t3, self.d1, self.d2, self.i1, self.i2)
-        # loss (truncated Chamfer means + BCE), dL/dd1, dL/dd2, the log entry, the counter
-        _lib.call("pcr_ndp_chamfer_glue", _lib.ptr(self.d1), self.K, _lib.ptr(self.d2), self.M,
-                  _lib.ptr(self.aux[self.nr_row] if self.bce_on else None), self.N, float(cfg.w_reg), 1e9,
-                  _lib.ptr(self.gd1), _lib.ptr(self.gd2), _lib.ptr(self.loss), _lib.ptr(self.log),
-                  _lib.ptr(self.ctr), int(cfg.iters), st)
+        if self.ldmk is not None:
+            # landmark mode: only the seeds dL/dd1, dL/dd2 of the Chamfer truncated at
+            # trunc_cd (w_cd enters through cd_scale); pcr_ndp_ldmk_loss makes the loss
+            sink, sink_ctr = self.glue_sink
+            _lib.call("pcr_ndp_chamfer_glue", _lib.ptr(self.d1), self.K, _lib.ptr(self.d2), self.M, None, self.N,
+                      0.0, float(cfg.trunc_cd), _lib.ptr(self.gd1), _lib.ptr(self.gd2), _lib.ptr(sink[0:1]),
+                      _lib.ptr(sink[1:2]), _lib.ptr(sink_ctr), 0, st)
+        else:
+            # loss (truncated Chamfer means + BCE), dL/dd1, dL/dd2, the log entry, the counter
+            _lib.call("pcr_ndp_chamfer_glue", _lib.ptr(self.d1), self.K, _lib.ptr(self.d2), self.M,
+                      _lib.ptr(self.aux[self.nr_row] if self.bce_on else None), self.N, float(cfg.w_reg), 1e9,
+                      _lib.ptr(self.gd1), _lib.ptr(self.gd2), _lib.ptr(self.loss), _lib.ptr(self.log),
+                      _lib.ptr(self.ctr), int(cfg.iters), st)
         nnd_backward_cuda(xs, self.t3, self.gsub, self.gt, self.gd1, self.gd2, self.i1, self.i2)
         if not self.use_inv:
             self.gx.zero_()
             self.gx.index_add_(0, self.inds, self.gsub[0])
 
 
+def _check_landmarks(landmarks):
+    """(src_ldmk, tgt_ldmk) as (L, 3) f32 numpy / tensors, L >= 1; ValueError otherwise."""
+    try:
+        a, b = landmarks
+    except (TypeError, ValueError):
+        raise ValueError("landmarks must be a pair (src_ldmk (L, 3), tgt_ldmk (L, 3))") from None
+    a, b = (torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v, dtype=torch.float32) for v in (a, b))
+    for name, v in (("src_ldmk", a), ("tgt_ldmk", b)):
+        if v.dim() != 2 or v.shape[1] != 3:
+            raise ValueError(f"landmarks: {name} must be (L, 3), got {tuple(v.shape)}")
+    if a.shape != b.shape:
+        raise ValueError(f"landmarks: {tuple(a.shape)} source against {tuple(b.shape)} target landmarks")
+    if a.shape[0] < 1:
+        raise ValueError("landmarks: at least one landmark pair is needed (L = 0)")
+    return a, b
+
+
 def optimize_deformation_pyramid(src_pcd, tgt_pcd, inds, config=None, NDP=None, use_graph=True,
-                                 fused=True):
+                                 fused=True, landmarks=None):
     """Returns (warped_pcd (N, 3) cuda f32, hist (levels + 1, N_s, 3) numpy, iter_cnt) like
     the reference, plus ``info`` per level {steps, evaluated, last_loss}.  ``NDP`` may be
     the reference's Deformation_Pyramid (any motion and rotation format; its layers
     say which) or this module's mirror; by default a fresh mirror is built from the
-    config (``motion_type``, ``rotation_format``), as the reference does."""
+    config (``motion_type``, ``rotation_format``), as the reference does.
+
+    ``landmarks = (src_ldmk (L, 3), tgt_ldmk (L, 3))``, coordinates in the frames of
+    ``src_pcd`` / ``tgt_pcd`` (L >= 1; ValueError otherwise), selects the landmark
+    branch of the reference (Registration.load_pcds(..., landmarks=...),
+    config/LNDP.yaml): mode "A" when ``config.w_cd > 0`` (landmark term +
+    w_cd * Chamfer of all samples truncated at ``config.trunc_cd``; ``inds`` is not
+    used), mode "B" otherwise (the landmark term alone: only the landmarks are
+    warped during the optimisation).  ``info[level]["mode"]`` says which (None without
+    landmarks) and ``info[level]["ldmk"]`` holds the level's warped landmarks +
+    tgt_mean, (L, 3); ``info[level]["chamfer"]`` is "none" in mode B (no Chamfer pass).  ``hist``: mode A as without landmarks; in mode B the
+    reference raises NameError where it records the level (registration.py:264:
+    ``s_sample_warped`` is never bound), so there is nothing to match and ``hist`` is
+    (1, N, 3), the final warp only."""
     cfg = NDPConfig.from_any(config or {})
+    if landmarks is not None:
+        landmarks = _check_landmarks(landmarks)
     if cfg.motion_type not in MOTIONS:
         raise ValueError(f"motion_type {cfg.motion_type!r} not in {MOTIONS}")
     if cfg.rotation_format not in ROTATION_FORMATS:
@@ -613,7 +731,14 @@ def optimize_deformation_pyramid(src_pcd, tgt_pcd, inds, config=None, NDP=None, 
     src_c = (src - src_mean).contiguous()
     s_sample = src_c.clone()
     t_sample = (tgt - tgt_mean).contiguous()
-    ind = torch.as_tensor(np.asarray(inds), dtype=torch.long, device=dev)
+    mode, n_ldmk = None, 0
+    if landmarks is None:
+        ind = torch.as_tensor(np.asarray(inds), dtype=torch.long, device=dev)
+    else:
+        # registration.py:186-187: centred by the means of the whole clouds
+        src_ldmk = (landmarks[0].to(dev) - src_mean).contiguous()
+        tgt_ldmk = (landmarks[1].to(dev) - tgt_mean).contiguous()
+        mode, n_ldmk, ind = "A" if cfg.w_cd > 0 else "B", src_ldmk.shape[0], None
     hist, info = [], []
     shared = {}  # per-pyramid buffers of the levels (_Level)
     for level in range(NDP.n_hierarchy):
@@ -621,7 +746,14 @@ def optimize_deformation_pyramid(src_pcd, tgt_pcd, inds, config=None, NDP=None, 
         layer = NDP.pyramid[level]
         use_fused = fused and layer.input[0].weight.shape[0] == 128
         t0 = time.perf_counter()
-        lv = (_LevelFused if use_fused else _Level)(layer, s_sample, t_sample, ind, level, cfg, shared)
+        if mode is None:
+            lv = (_LevelFused if use_fused else _Level)(layer, s_sample, t_sample, ind, level, cfg, shared)
+        else:
+            # the level's input, landmarks first (registration.py:214): one allocation
+            # per level, outside the capture
+            x_in = torch.cat([src_ldmk, s_sample]) if mode == "A" else src_ldmk
+            lv = (_LevelFused if use_fused else _Level)(layer, x_in, t_sample, ind, level, cfg, shared,
+                                                        ldmk=(n_ldmk, tgt_ldmk, mode))
         t1 = time.perf_counter()
         lv.run(use_graph)
         st = lv.state.cpu().numpy()
@@ -631,7 +763,8 @@ def optimize_deformation_pyramid(src_pcd, tgt_pcd, inds, config=None, NDP=None, 
                      # which path ran: the fused HIP MLP kernels (width 128) or torch
                      # autograd, and the fused level Chamfer or the nnd drop-in kernels
                      "mlp": "fused" if use_fused else "torch",
-                     "chamfer": "fused" if getattr(lv, "use_nc", False) else "nnd"})
+                     "chamfer": "none" if mode == "B" else "fused" if getattr(lv, "use_nc", False) else "nnd",
+                     "mode": mode})
         ev = getattr(lv, "replay_events", None)
         if ev is not None:
             info[-1]["replay_ms"] = ev[0].elapsed_time(ev[1])
@@ -646,8 +779,17 @@ def optimize_deformation_pyramid(src_pcd, tgt_pcd, inds, config=None, NDP=None, 
                 info[-1]["nc_stats"] = [int(v) for v in hdr[64:88].view(np.uint64)]
         info[-1]["setup_ms"] = (t1 - t0) * 1e3
         info[-1]["level_ms"] = (t2 - t0) * 1e3
-        hist.append((lv.warped + tgt_mean).cpu().numpy())
-        s_sample = lv.warped.clone()
+        if mode is None:
+            hist.append((lv.warped + tgt_mean).cpu().numpy())
+            s_sample = lv.warped.clone()
+        else:
+            # registration.py:266-270: the warped landmarks feed the next level in both
+            # modes, the warped samples in mode A only
+            src_ldmk = lv.warped[:n_ldmk].clone()
+            info[-1]["ldmk"] = (src_ldmk + tgt_mean).cpu().numpy()
+            if mode == "A":
+                s_sample = lv.warped[n_ldmk:].clone()
+                hist.append((s_sample + tgt_mean).cpu().numpy())
     NDP.gradient_setup(optimized_level=-1)
     warped, _ = warp_pyramid(NDP, src_c)
     warped = warped + tgt_mean
