@@ -7,27 +7,9 @@ import numpy as np
 import pytest
 
 from pointcloudregistration_amd import geometry, registration as reg, synth
+from voxel_cases import _numpy_groups, sorted_rows as _sorted_rows
 
 pytestmark = pytest.mark.gpu
-
-
-def _numpy_groups(pts, voxel):
-    vmin = pts.min(0) - voxel * 0.5
-    keys = np.floor((pts - vmin) / voxel).astype(np.int64)
-    uk, inv = np.unique(keys, axis=0, return_inverse=True)
-    inv = inv.reshape(-1)
-    means = np.zeros((len(uk), 3))
-    for k in range(len(uk)):
-        rows = pts[inv == k]
-        s = np.zeros(3)
-        for r in rows:          # input order, sequential f64 (AccumulatedPoint)
-            s = s + r
-        means[k] = s / float(len(rows))
-    return means
-
-
-def _sorted_rows(a):
-    return a[np.lexsort(a.T[::-1])]
 
 
 @pytest.mark.parametrize("n,voxel,scale", [(10000, 1.0, 40.0), (3000, 0.05, 1.0), (20000, 0.025, 1.0),
