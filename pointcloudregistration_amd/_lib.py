@@ -160,6 +160,38 @@ SIGNATURES = {
     "pcr_pointwise_forward": [ctypes.POINTER(PointwiseArgs), _p, _p],
 }
 
+_pi64 = ctypes.POINTER(_i64)
+# name -> (restype, argtypes) of every entry point that does not return a pcr status as c_int
+# through SIGNATURES: sizes, counters, the profile, the error text, teardown
+OTHER_SIGNATURES = {
+    "pcr_last_error": (ctypes.c_char_p, []),
+    "pcr_version": (ctypes.c_int, []),
+    "pcr_workspace_release": (ctypes.c_int, []),
+    "pcr_profile_enable": (None, [_i32]),
+    "pcr_profile_read": (ctypes.c_int, [_i32, ctypes.POINTER(_f64), _pi64, _i32]),
+    "pcr_featnn_rescan_rows": (ctypes.c_int, [_pi64, _pi64, _i32]),
+    "pcr_featnn_fallback_rows": (ctypes.c_int, [_pi64, _pi64, _i32]),
+    "pcr_featnn_image_chunks": (ctypes.c_int, [ctypes.POINTER(_i32)]),
+    "pcr_ndp_train_partial_floats": (_i64, [_i32] * 4),
+    "pcr_ndp_train_partial_floats_head": (_i64, [_i32] * 5),
+    "pcr_ndp_head_rows": (_i32, [_i32] * 2),
+    "pcr_ndp_chamfer_scratch_bytes": (_i64, [_i32] * 2),
+    "pcr_ndp_loss_scratch_bytes": (_i64, []),
+    "pcr_ndp_ldmk_loss_scratch_bytes": (_i64, []),
+    "pcr_ndp_chamfer_gacc_words": (_i64, [_i32]),
+    "pcr_ndp_chamfer_max_points": (_i32, []),
+    "pcr_tfmr_scratch_bytes": (_i64, [_i32] * 5),
+    "pcr_cpd_scratch_bytes": (_i64, [_i32] * 3),
+    "pcr_attention_scratch_bytes": (_i64, [_i32] * 6),
+    "pcr_offset_attention_scratch_bytes": (_i64, [_i32] * 4),
+    "pcr_pointnet_scratch_bytes": (_i64, [_i32] * 3),
+    "pcr_edge_conv_scratch_bytes": (_i64, [_i32] * 5),
+    "pcr_group_mlp_scratch_bytes": (_i64, [_i32] * 7),
+    "pcr_unary_scratch_bytes": (_i64, [_i32] * 2),
+    "pcr_pointwise_scratch_bytes": (_i64, [_i32] * 3),
+    "pcr_shutdown": (ctypes.c_int, []),
+}
+
 
 def load():
     """Load libpcr.so once; raise PcrError (no fallback) if it cannot be loaded."""
@@ -178,60 +210,13 @@ def load():
             lib = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise PcrError(f"failed to load {LIB_PATH}: {e}") from e
-        lib.pcr_last_error.restype = ctypes.c_char_p
-        lib.pcr_last_error.argtypes = []
-        lib.pcr_version.restype = ctypes.c_int
-        lib.pcr_workspace_release.restype = ctypes.c_int
-        lib.pcr_workspace_release.argtypes = []
-        lib.pcr_profile_enable.restype = None
-        lib.pcr_profile_enable.argtypes = [_i32]
-        lib.pcr_profile_read.restype = ctypes.c_int
-        lib.pcr_profile_read.argtypes = [_i32, ctypes.POINTER(_f64), ctypes.POINTER(_i64), _i32]
-        lib.pcr_featnn_rescan_rows.restype = ctypes.c_int
-        lib.pcr_featnn_rescan_rows.argtypes = [ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32]
-        lib.pcr_featnn_fallback_rows.restype = ctypes.c_int
-        lib.pcr_featnn_fallback_rows.argtypes = [ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32]
-        lib.pcr_featnn_image_chunks.restype = ctypes.c_int
-        lib.pcr_featnn_image_chunks.argtypes = [ctypes.POINTER(_i32)]
-        lib.pcr_ndp_train_partial_floats.restype = _i64
-        lib.pcr_ndp_train_partial_floats.argtypes = [_i32, _i32, _i32, _i32]
-        lib.pcr_ndp_train_partial_floats_head.restype = _i64
-        lib.pcr_ndp_train_partial_floats_head.argtypes = [_i32, _i32, _i32, _i32, _i32]
-        lib.pcr_ndp_head_rows.restype = _i32
-        lib.pcr_ndp_head_rows.argtypes = [_i32, _i32]
-        lib.pcr_ndp_chamfer_scratch_bytes.restype = _i64
-        lib.pcr_ndp_chamfer_scratch_bytes.argtypes = [_i32, _i32]
-        lib.pcr_ndp_loss_scratch_bytes.restype = _i64
-        lib.pcr_ndp_loss_scratch_bytes.argtypes = []
-        lib.pcr_ndp_ldmk_loss_scratch_bytes.restype = _i64
-        lib.pcr_ndp_ldmk_loss_scratch_bytes.argtypes = []
-        lib.pcr_ndp_chamfer_gacc_words.restype = _i64
-        lib.pcr_ndp_chamfer_gacc_words.argtypes = [_i32]
-        lib.pcr_ndp_chamfer_max_points.restype = _i32
-        lib.pcr_ndp_chamfer_max_points.argtypes = []
-        lib.pcr_tfmr_scratch_bytes.restype = _i64
-        lib.pcr_tfmr_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32]
-        lib.pcr_cpd_scratch_bytes.restype = _i64
-        lib.pcr_cpd_scratch_bytes.argtypes = [_i32, _i32, _i32]
-        lib.pcr_attention_scratch_bytes.restype = _i64
-        lib.pcr_attention_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32]
-        lib.pcr_offset_attention_scratch_bytes.restype = _i64
-        lib.pcr_offset_attention_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32]
-        lib.pcr_pointnet_scratch_bytes.restype = _i64
-        lib.pcr_pointnet_scratch_bytes.argtypes = [_i32, _i32, _i32]
-        lib.pcr_edge_conv_scratch_bytes.restype = _i64
-        lib.pcr_edge_conv_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32]
-        lib.pcr_group_mlp_scratch_bytes.restype = _i64
-        lib.pcr_group_mlp_scratch_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, _i32]
-        lib.pcr_unary_scratch_bytes.restype = _i64
-        lib.pcr_unary_scratch_bytes.argtypes = [_i32, _i32]
-        lib.pcr_pointwise_scratch_bytes.restype = _i64
-        lib.pcr_pointwise_scratch_bytes.argtypes = [_i32, _i32, _i32]
-        lib.pcr_shutdown.restype = ctypes.c_int
-        lib.pcr_shutdown.argtypes = []
         for name, args in SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype = ctypes.c_int
+            fn.argtypes = args
+        for name, (res, args) in OTHER_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
             fn.argtypes = args
         _lib = lib
         # free the library's device objects (workspace, profiling events) at
@@ -242,16 +227,7 @@ def load():
 
 
 def exported_symbols():
-    return ["pcr_last_error", "pcr_version", "pcr_workspace_release", "pcr_profile_enable", "pcr_profile_read",
-            "pcr_featnn_rescan_rows", "pcr_featnn_fallback_rows", "pcr_featnn_image_chunks", "pcr_ndp_train_partial_floats", "pcr_ndp_train_partial_floats_head", "pcr_ndp_head_rows",
-            "pcr_ndp_chamfer_scratch_bytes",
-            "pcr_ndp_loss_scratch_bytes", "pcr_ndp_ldmk_loss_scratch_bytes", "pcr_ndp_chamfer_gacc_words",
-            "pcr_ndp_chamfer_max_points",
-            "pcr_tfmr_scratch_bytes", "pcr_cpd_scratch_bytes", "pcr_attention_scratch_bytes",
-            "pcr_offset_attention_scratch_bytes", "pcr_pointnet_scratch_bytes", "pcr_edge_conv_scratch_bytes",
-            "pcr_group_mlp_scratch_bytes", "pcr_unary_scratch_bytes", "pcr_pointwise_scratch_bytes",
-            "pcr_shutdown"] + \
-        list(SIGNATURES)
+    return list(OTHER_SIGNATURES) + list(SIGNATURES)
 
 
 PROF_FEAT_SCREEN, PROF_NND_FWD, PROF_RANSAC_VALIDATE, PROF_ICP, PROF_RANSAC_HYP = 0, 1, 2, 3, 4

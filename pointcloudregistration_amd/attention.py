@@ -36,7 +36,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _front, _lib
 
 __all__ = ["multi_head_attention", "overlap_scores", "offset_attention", "CrossAttention",
            "OverlapAttentionBlock", "fuse", "MAX_CHANNELS"]
@@ -45,25 +45,9 @@ MAX_CHANNELS = 256   # d and dv (pcr_api.h)
 MAX_TOKENS = 1 << 24
 
 
-def _forward_only(what, *tensors):
-    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
-        raise RuntimeError(f"{what} is forward-only (inference): call it under torch.no_grad() or pass "
-                           "detached tensors; it would otherwise silently cut the graph")
-
-
-def _f32(t, name, ndim):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) "
-                         "library and this module has no CPU path")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
-    if t.dim() != ndim:
-        raise ValueError(f"{name} must have {ndim} dimensions, got {tuple(t.shape)}")
-    t = t.detach()
+def _f32(t, name, phrase, ndim, dev=None):
     # unit token stride goes in by stride; anything else is copied once
-    return t if t.shape[-1] <= 1 or t.stride(-1) == 1 else t.contiguous()
+    return _front.tensor(t, name, phrase, ndim, dev, "f32", _front.unit_last)
 
 
 def _channels(name, c):
@@ -71,18 +55,12 @@ def _channels(name, c):
         raise ValueError(f"{name}={c} channels outside 1..{MAX_CHANNELS}")
 
 
-def _scratch(nbytes, dev):
-    if nbytes < 0:
-        raise _lib.PcrError(_lib.load().pcr_last_error().decode("utf-8", "replace"))
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-
-
 def _attention(q, k, v, out, b, h, n, m, d, dv, scale, strides):
     """One pcr_attention_forward; strides = (q, k, v, out) x (batch, head, channel)."""
     lib = _lib.load()
     dev = q.device
     with torch.cuda.device(dev):
-        ws = _scratch(lib.pcr_attention_scratch_bytes(b, h, n, m, d, dv), dev)
+        ws = _front.scratch(lib.pcr_attention_scratch_bytes(b, h, n, m, d, dv), dev)
         args = []
         for t, st in zip((q, k, v, out), strides):
             args += [_lib.ptr(t), *st]
@@ -95,16 +73,15 @@ def multi_head_attention(query, key, value):
     key (B, dim, nhead, M), value (B, dv, nhead, M) -> (B, dv, nhead, N), the scale
     1 / sqrt(dim).  No (B, nhead, N, M) tensor: the output, and where the grid is
     small a scratch of the output's order."""
-    _forward_only("multi_head_attention", query, key, value)
-    q, k, v = _f32(query, "query", 4), _f32(key, "key", 4), _f32(value, "value", 4)
+    _front.forward_only("multi_head_attention", query, key, value)
+    q = _f32(query, "query", "(B, dim, nhead, N)", 4)
+    k, v = _f32(key, "key", "(B, dim, nhead, M)", 4, q.device), _f32(value, "value", "(B, dv, nhead, M)", 4, q.device)
     b, d, h, n = q.shape
     m, dv = k.shape[3], v.shape[1]
     if k.shape[:3] != (b, d, h):
         raise ValueError(f"key {tuple(k.shape)} must be (B={b}, dim={d}, nhead={h}, M)")
     if v.shape[0] != b or v.shape[2] != h or v.shape[3] != m:
         raise ValueError(f"value {tuple(v.shape)} must be (B={b}, dv, nhead={h}, M={m})")
-    if k.device != q.device or v.device != q.device:
-        raise ValueError("all inputs must live on one device")
     _channels("dim", d)
     _channels("dv", dv)
     if h < 1:
@@ -130,18 +107,16 @@ def overlap_scores(feats_norm, attn_scores, len_src, temperature):
     never formed.  feats_norm is taken in place when it is the transposed view
     of a (C, n) tensor (stride 1 along n), as the reference passes it.
     `temperature` may be a one-element tensor (read once, on the host)."""
-    _forward_only("overlap_scores", feats_norm, attn_scores)
+    _front.forward_only("overlap_scores", feats_norm, attn_scores)
     f = feats_norm
     if isinstance(f, torch.Tensor) and f.dim() == 2:
         f = f.t()                                   # (C, n): channel-major
-    f = _f32(f, "feats_norm", 2)
+    f = _f32(f, "feats_norm", "(n, C)", 2)
     c, n = f.shape
     a = attn_scores
     if not isinstance(a, torch.Tensor) or a.dim() != 2 or a.shape != (n, 1):
         raise ValueError(f"attn_scores must be (n={n}, 1)")
-    a = _f32(a.t(), "attn_scores", 2)               # (1, n)
-    if a.device != f.device:
-        raise ValueError("all inputs must live on one device")
+    a = _f32(a.t(), "attn_scores", "(n, 1)", 2, f.device)   # (1, n)
     _channels("C", c)
     n1 = int(len_src)
     if not 0 < n1 < n:
@@ -165,8 +140,9 @@ def offset_attention(x_q, x_k, x_v, ol_score=None):
       a_ij = ol_i <x_q[:, i], x_k[:, j]>,  P = softmax_j a,
       x_r[:, j] = sum_i x_v[:, i] P_ij / (1e-9 + sum_i P_ij).
     Two sweeps over the scores, neither stores them: the scratch is 8 B N bytes."""
-    _forward_only("offset_attention", x_q, x_k, x_v, ol_score)
-    q, k, v = _f32(x_q, "x_q", 3), _f32(x_k, "x_k", 3), _f32(x_v, "x_v", 3)
+    _front.forward_only("offset_attention", x_q, x_k, x_v, ol_score)
+    q = _f32(x_q, "x_q", "(B, d, N)", 3)
+    k, v = _f32(x_k, "x_k", "(B, d, N)", 3, q.device), _f32(x_v, "x_v", "(B, C, N)", 3, q.device)
     b, d, n = q.shape
     dv = v.shape[1]
     if k.shape != q.shape:
@@ -175,11 +151,9 @@ def offset_attention(x_q, x_k, x_v, ol_score=None):
         raise ValueError(f"x_v {tuple(v.shape)} must be (B={b}, C, N={n})")
     r = None
     if ol_score is not None:
-        r = _f32(ol_score, "ol_score", 2)
+        r = _f32(ol_score, "ol_score", "(B, N)", 2, q.device)
         if r.shape != (b, n):
             raise ValueError(f"ol_score {tuple(r.shape)} must be (B={b}, N={n})")
-    if any(t.device != q.device for t in (k, v) + ((r,) if r is not None else ())):
-        raise ValueError("all inputs must live on one device")
     _channels("d", d)
     _channels("C", dv)
     if n > MAX_TOKENS:
@@ -190,7 +164,7 @@ def offset_attention(x_q, x_k, x_v, ol_score=None):
     lib = _lib.load()
     dev = q.device
     with torch.cuda.device(dev):
-        ws = _scratch(lib.pcr_offset_attention_scratch_bytes(b, n, d, dv), dev)
+        ws = _front.scratch(lib.pcr_offset_attention_scratch_bytes(b, n, d, dv), dev)
         _lib.call("pcr_offset_attention_forward", _lib.ptr(q), q.stride(0), q.stride(1), _lib.ptr(k),
                   k.stride(0), k.stride(1), _lib.ptr(v), v.stride(0), v.stride(1), _lib.ptr(r),
                   r.stride(0) if r is not None else 0, _lib.ptr(out), out.stride(0), out.stride(1), b, n, d,
@@ -261,10 +235,6 @@ class OverlapAttentionBlock(torch.nn.Module):
         return x + x_r
 
 
-def _has(mod, *names):
-    return all(hasattr(mod, n) for n in names)
-
-
 def fuse(model):
     """Swap a loaded network's attention blocks for the fused ones, in place: every
     child of class name `Cross_Attention` with q_conv, k_conv, v_conv, conv, mlp,
@@ -274,22 +244,8 @@ def fuse(model):
     submodules, so parameters (and the q/k weight tying) are shared, not
     copied.  Returns (cross-attention blocks swapped, overlap blocks swapped); a
     second call finds nothing and returns (0, 0)."""
-    n_cross = n_offset = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if isinstance(child, (CrossAttention, OverlapAttentionBlock)):
-                continue
-            cls = type(child).__name__
-            if cls == "Cross_Attention" and _has(child, "q_conv", "k_conv", "v_conv", "conv", "mlp", "nhead",
-                                                 "feats_dim"):
-                new = CrossAttention(child.feats_dim, child.nhead, like=child)
-                n_cross += 1
-            elif cls == "OverlapAttentionBlock" and _has(child, "q_conv", "k_conv", "v_conv", "trans_conv",
-                                                         "after_norm", "act"):
-                new = OverlapAttentionBlock(child.v_conv.in_channels, like=child)
-                n_offset += 1
-            else:
-                continue
-            new.train(child.training)
-            setattr(parent, name, new)
-    return n_cross, n_offset
+    kinds = ((("Cross_Attention", ("q_conv", "k_conv", "v_conv", "conv", "mlp", "nhead", "feats_dim")),
+              lambda c: CrossAttention(c.feats_dim, c.nhead, like=c)),
+             (("OverlapAttentionBlock", ("q_conv", "k_conv", "v_conv", "trans_conv", "after_norm", "act")),
+              lambda c: OverlapAttentionBlock(c.v_conv.in_channels, like=c)))
+    return _front.swap_children(model, kinds, errors=(), skip=(CrossAttention, OverlapAttentionBlock))

@@ -52,8 +52,8 @@
 namespace {
 
 using pcr::cdiv64;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using pcr::f32x16;
+using pcr::tile_row;
 
 constexpr int kThreads = 256;
 constexpr int kLaneTile = 128;   // lane-side positions per workgroup
@@ -77,9 +77,6 @@ struct AttnArgs {
     float scale;
     int nlt, ndvc, nsplit, tps;               // lane tiles, dv chunks, splits, tiles per split
 };
-
-// row of the 32x32 tile held in register r of lane half hh
-__device__ __forceinline__ int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 template <int MODE, int DQ, bool NARROW>
 __global__ __launch_bounds__(kThreads) void attn(AttnArgs a) {

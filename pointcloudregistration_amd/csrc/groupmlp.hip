@@ -53,8 +53,8 @@ using pcr::kFinRuns;
 using pcr::kFinThreads;
 using pcr::norm_finalize;
 using pcr::WsLayout;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using pcr::f32x16;
+using pcr::tile_row;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 64;       // rows per tile
@@ -67,9 +67,6 @@ constexpr int kMaxB = 65535;    // gridDim.y
 constexpr int kXLd = kMaxCin + 1;
 constexpr int kWaveBlk = kMaxC / 32 / 4;  // channel blocks per wave
 constexpr int kEdgePts = 8;     // points per edge_reduce workgroup: its statistics tile
-
-// row of the 32x32 tile held in accumulator register r of lane half hh
-__device__ __forceinline__ int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 __device__ __forceinline__ float act(float v, float slope) {
     return v > 0.0f ? v : (slope == 0.0f ? 0.0f : __fmul_rn(v, slope));

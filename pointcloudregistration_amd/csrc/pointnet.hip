@@ -45,8 +45,8 @@
 namespace {
 
 using pcr::cdiv64;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using pcr::f32x16;
+using pcr::tile_row;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 64;      // points per tile
@@ -60,9 +60,6 @@ constexpr int kMaxDim = 256;
 constexpr int kMaxP = 4096;
 constexpr int kMaxB = 1 << 20;
 constexpr int kMaxPointBlocks = 512;  // two workgroups per CU
-
-// row of the 32x32 tile held in accumulator register r of lane half hh
-__device__ __forceinline__ int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 struct PointArgs {
     const float *x; long long sb, sc, sp;  // element (b, coord, point)

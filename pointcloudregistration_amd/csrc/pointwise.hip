@@ -45,8 +45,8 @@ using pcr::kFinRuns;
 using pcr::kFinThreads;
 using pcr::norm_finalize_groups;
 using pcr::WsLayout;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using pcr::f32x16;
+using pcr::tile_row;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 64;         // points per tile: the statistics' tile
@@ -67,9 +67,6 @@ constexpr int kSmallK = 128;                      // its inputs staged at a time
 constexpr int kSmallLd = kSmallK + 1;
 constexpr int kSmallWPer = kSmallO * kSmallK / kThreads;  // 32 staged weight elements per thread
 constexpr int kWPer = kChan * kChunk / kThreads;  // 16 staged weight elements
-
-// channel of the 32x32 tile held in accumulator register r of lane half hh
-__device__ __forceinline__ int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 struct Args {
     const float *src[kSrc], *sub[kSrc];

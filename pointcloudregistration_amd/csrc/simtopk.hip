@@ -35,8 +35,7 @@
 namespace {
 
 using pcr::cdiv64, pcr::u64;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using pcr::f32x16;
 
 constexpr int kSimThreads = 256;
 constexpr int kSimTile = 128;              // sources and targets per workgroup

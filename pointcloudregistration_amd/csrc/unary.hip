@@ -40,8 +40,8 @@ using pcr::kFinRuns;
 using pcr::kFinThreads;
 using pcr::norm_finalize;
 using pcr::WsLayout;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using pcr::f32x16;
+using pcr::tile_row;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 64;        // rows per tile: the statistics' tile
@@ -54,9 +54,6 @@ constexpr int kMaxCin = 2048;
 constexpr int kMaxCout = 1024;
 constexpr int kXPer = kTile * kChunk / kThreads;  // 8 staged row elements per thread
 constexpr int kWPer = kChan * kChunk / kThreads;  // 16 staged weight elements
-
-// row of the 32x32 tile held in accumulator register r of lane half hh
-__device__ __forceinline__ int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 struct Args {
     const float *x0, *x1, *w, *bias, *res, *coef;

@@ -1,5 +1,6 @@
 // Device / launch helpers that units used to carry copies of: wave64 butterfly
-// reductions, the block-wide bounding-box reduction, a few one-line functions.
+// reductions, the block-wide bounding-box reduction, the 32x32 MFMA accumulator's
+// row map, a few one-line functions.
 // Header only; HIP units only (it calls __shfl_xor).  A kernel whose device
 // code is pinned keeps its written-out butterfly: the same loop behind an
 // inlined call schedules differently.
@@ -10,6 +11,11 @@
 namespace pcr {
 
 typedef unsigned long long u64;
+
+// The 32x32 f32 MFMA accumulator: 16 registers per lane.  Lane l holds column
+// l & 31; register r of lane half hh = l >> 5 holds the row tile_row(r, hh).
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 // Wave reduce: the xor butterfly, offsets 32 down to 1, result in every lane.
 // One fixed order, so a floating-point sum has the same bits wherever it is

@@ -41,26 +41,19 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _front, _lib
 
 __all__ = ["fps", "gather_points", "ball_query", "sample_and_group", "local_ppf_features",
            "knn_graph", "graph_features"]
 
 
 def _cloud(name, t, last=3):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) "
-                         "library and this module has no CPU path")
-    if t.dim() != 3 or (last is not None and t.shape[2] != last) or t.shape[2] < 1:
-        raise ValueError(f"{name} must be (B, N, {last or 'C'}), got {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
-    if t.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError(f"{name} requires grad: the grouping ops are forward-only; call them "
-                           "under torch.no_grad() or pass a detached tensor")
-    return t.contiguous()
+    _front.tensor(t, name, "(B, N, {2})" if last else "(B, N, C)", (None, None, last))
+    if t.shape[2] < 1:
+        raise ValueError(f"{name} must be (B, N, C), got {tuple(t.shape)} without channels")
+    _front.forward_only(name, t, message=f"{name} requires grad: the grouping ops are forward-only; call them "
+                        "under torch.no_grad() or pass a detached tensor")
+    return t.contiguous()   # the caller's own tensor: sample_and_group hands it back
 
 
 def _r2(radius):
@@ -139,8 +132,7 @@ def sample_and_group(xyz, points, M, radius, K, use_xyz=True, rt_density=False):
     (centred on ``new_xyz``) and, with ``rt_density``, the density.  ``M < 0``
     makes every point a centre."""
     xyz = _cloud("xyz", xyz)
-    if points is not None and points.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("points requires grad: the grouping ops are forward-only")
+    _front.forward_only("points", points, message="points requires grad: the grouping ops are forward-only")
     new_xyz = xyz if M < 0 else gather_points(xyz, fps(xyz, M))
     res = ball_query(xyz, new_xyz, radius, K, rt_density=rt_density)
     grouped_inds, density = res if rt_density else (res, None)

@@ -30,8 +30,7 @@ import ctypes
 
 import torch
 
-from . import _lib, grouping
-from .attention import _forward_only, _scratch
+from . import _front, _lib, grouping
 
 __all__ = ["edge_conv", "group_mlp", "GCN", "PPF", "LocalFeature", "fuse", "MAX_WIDTH", "MAX_GROUP",
            "MAX_GROUP_CHANNELS", "MAX_NEIGHBOURS"]
@@ -43,21 +42,6 @@ MAX_NEIGHBOURS = 63        # kk
 _MAX_POINTS = 1 << 20
 _MAX_BATCH = 65535
 _STAGES = {"edge": ("rq", "stats"), "mlp": ("y1", "y2", "y3", "stats1", "stats2", "stats3")}
-
-
-def _tensor(t, name, ndim, dev=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) "
-                         "library and this module has no CPU path")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
-    if t.dim() != ndim:
-        raise ValueError(f"{name} must have {ndim} dimensions, got {tuple(t.shape)}")
-    if dev is not None and t.device != dev:
-        raise ValueError(f"{name} on {t.device}, expected {dev}: all inputs must live on one device")
-    return t.detach()
 
 
 def _width(name, c):
@@ -74,7 +58,7 @@ def _sizes(b, n):
 
 def _conv_weight(w, name, dev):
     """(out, in) view of a Conv2d / Conv1d 1x1 weight or a matrix, on its own storage."""
-    w = _tensor(w, name, w.dim() if isinstance(w, torch.Tensor) else 2, dev)
+    w = _front.tensor(w, name, "(out, in)", None, dev)
     if w.dim() > 2:
         if any(s != 1 for s in w.shape[2:]):
             raise ValueError(f"{name}: only 1x1 kernels, got {tuple(w.shape)}")
@@ -82,14 +66,6 @@ def _conv_weight(w, name, dev):
     if w.dim() != 2:
         raise ValueError(f"{name} must be (out, in), got {tuple(w.shape)}")
     return w.contiguous()
-
-
-def _want(want, kind):
-    want = tuple(want)
-    for name in want:
-        if name not in _STAGES[kind]:
-            raise ValueError(f"want: unknown output {name!r} (one of {', '.join(_STAGES[kind])})")
-    return want
 
 
 def edge_conv(feats, inds, weight, slope=0.2, eps=1e-5, channels_first=False, want=()):
@@ -102,8 +78,8 @@ def edge_conv(feats, inds, weight, slope=0.2, eps=1e-5, channels_first=False, wa
     ``(B, C', N)`` with ``channels_first``.  C, C' multiples of 32, at most 512.
     want: names among "rq" ``(B, N, 2C')`` (``R = P - Q | Q``) and "stats"
     ``(B, C', 2)`` f64 (mean, var), appended to the result."""
-    _forward_only("groupmlp.edge_conv", feats, weight)
-    f = _tensor(feats, "feats", 3)
+    _front.forward_only("groupmlp.edge_conv", feats, weight)
+    f = _front.tensor(feats, "feats", "(B, C, N)" if channels_first else "(B, N, C)", 3)
     dev = f.device
     if channels_first:
         f = f.transpose(1, 2)
@@ -122,7 +98,7 @@ def edge_conv(feats, inds, weight, slope=0.2, eps=1e-5, channels_first=False, wa
     kk = inds.shape[2]
     if not 1 <= kk <= MAX_NEIGHBOURS:
         raise ValueError(f"kk={kk} outside 1..{MAX_NEIGHBOURS}")
-    want = _want(want, "edge")
+    want = _front.wanted(want, _STAGES["edge"])
     idx = inds.to(torch.int32).contiguous()
     out = torch.empty((b, co, n) if channels_first else (b, n, co), dtype=torch.float32, device=dev)
     shapes = {"rq": ((b, n, 2 * co), torch.float32), "stats": ((b, co, 2), torch.float64)}
@@ -130,7 +106,7 @@ def edge_conv(feats, inds, weight, slope=0.2, eps=1e-5, channels_first=False, wa
     if b:
         lib = _lib.load()
         with torch.cuda.device(dev):
-            ws = _scratch(lib.pcr_edge_conv_scratch_bytes(b, n, kk, c, co), dev)
+            ws = _front.scratch(lib.pcr_edge_conv_scratch_bytes(b, n, kk, c, co), dev)
             _lib.call("pcr_edge_conv", _lib.ptr(f), f.stride(0), f.stride(1), f.stride(2), _lib.ptr(idx), b, n, kk,
                       c, co, _lib.ptr(w), float(eps), float(slope), 1 if channels_first else 0, _lib.ptr(out),
                       _lib.ptr(outs.get("rq")), _lib.ptr(outs.get("stats")), _lib.ptr(ws), _lib.stream_handle(dev))
@@ -160,11 +136,11 @@ def group_mlp(x, weights, norm="instance", gammas=None, betas=None, eps=1e-5, sl
     betas = list(betas) if betas is not None else [None] * nl
     if len(gammas) != nl or len(betas) != nl:
         raise ValueError("gammas and betas must have one entry (a tensor or None) per layer")
-    _forward_only("groupmlp.group_mlp", x, *weights, *gammas, *betas)
+    _front.forward_only("groupmlp.group_mlp", x, *weights, *gammas, *betas)
     if norm not in ("instance", "group"):
         raise ValueError(f"norm={norm!r}: 'instance' or 'group'")
     group = 1 if norm == "instance" else 32
-    xt = _tensor(x, "x", 4).contiguous()
+    xt = _front.tensor(x, "x", "(B, N, K, cin)", 4).contiguous()
     dev = xt.device
     b, n, k, cin = xt.shape
     _sizes(b, n)
@@ -172,7 +148,7 @@ def group_mlp(x, weights, norm="instance", gammas=None, betas=None, eps=1e-5, sl
         raise ValueError(f"K={k} outside 1..{MAX_GROUP}")
     if not 1 <= cin <= MAX_GROUP_CHANNELS:
         raise ValueError(f"cin={cin} outside 1..{MAX_GROUP_CHANNELS}")
-    want = _want(want, "mlp")
+    want = _front.wanted(want, _STAGES["mlp"])
     net = _lib.GroupMlpNet()
     net.layers = nl
     keep, widths, prev = [], [], cin
@@ -188,7 +164,7 @@ def group_mlp(x, weights, norm="instance", gammas=None, betas=None, eps=1e-5, sl
         net.w[i] = w.data_ptr()
         for arr, src, what in ((net.gamma, gammas[i], "gammas"), (net.beta, betas[i], "betas")):
             if src is not None:
-                t = _tensor(src, f"{what}[{i}]", 1, dev).contiguous()
+                t = _front.tensor(src, f"{what}[{i}]", "(c,)", 1, dev).contiguous()
                 if t.shape[0] != prev:
                     raise ValueError(f"{what}[{i}] has {t.shape[0]} entries, layer {i + 1} {prev} channels")
                 keep.append(t)
@@ -210,7 +186,7 @@ def group_mlp(x, weights, norm="instance", gammas=None, betas=None, eps=1e-5, sl
         lib = _lib.load()
         c3 = widths + [0, 0]
         with torch.cuda.device(dev):
-            ws = _scratch(lib.pcr_group_mlp_scratch_bytes(b, n, k, nl, c3[0], c3[1], c3[2]), dev)
+            ws = _front.scratch(lib.pcr_group_mlp_scratch_bytes(b, n, k, nl, c3[0], c3[1], c3[2]), dev)
             _lib.call("pcr_group_mlp", _lib.ptr(xt), b, n, k, cin, ctypes.byref(net), group, float(eps),
                       float(slope), 1 if channels_first else 0, _lib.ptr(out), _lib.ptr(ws),
                       _lib.stream_handle(dev))
@@ -339,10 +315,6 @@ class LocalFeature(torch.nn.Module):
         return group_mlp(group, **_mlp_plan(self.local_feature_fused, "LocalFeatue.local_feature_fused"))
 
 
-def _has(mod, *names):
-    return all(hasattr(mod, n) for n in names)
-
-
 def fuse(model, refused=None):
     """Swap a loaded network's blocks for the fused ones, in place: every child of class name
     `GCN` with conv1, conv2, conv3 and k, every `PPF` with k, radius and local_feature_fused,
@@ -351,25 +323,7 @@ def fuse(model, refused=None):
     statistics, or whose structure is not conv -> norm -> activation, is left in place; its
     name and the reason are appended to `refused` (a list) when one is given.  Returns
     (GCN, PPF, LocalFeatue) blocks swapped; a second call finds nothing and returns zeros."""
-    kinds = (("GCN", GCN, ("conv1", "conv2", "conv3", "k")),
-             ("PPF", PPF, ("k", "radius", "local_feature_fused")),
-             ("LocalFeatue", LocalFeature, ("radius", "K", "local_feature_fused")))
-    counts = [0, 0, 0]
-    for pname, parent in list(model.named_modules()):
-        for name, child in list(parent.named_children()):
-            if isinstance(child, (GCN, PPF, LocalFeature)):
-                continue
-            for i, (cls, new_type, attrs) in enumerate(kinds):
-                if type(child).__name__ != cls or not _has(child, *attrs):
-                    continue
-                try:
-                    new = new_type(child)
-                except ValueError as e:
-                    if refused is not None:
-                        refused.append((f"{pname}.{name}" if pname else name, str(e)))
-                    break
-                new.train(child.training)
-                setattr(parent, name, new)
-                counts[i] += 1
-                break
-    return tuple(counts)
+    kinds = ((("GCN", ("conv1", "conv2", "conv3", "k")), GCN),
+             (("PPF", ("k", "radius", "local_feature_fused")), PPF),
+             (("LocalFeatue", ("radius", "K", "local_feature_fused")), LocalFeature))
+    return _front.swap_children(model, kinds, refused=refused, skip=(GCN, PPF, LocalFeature))

@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _front, _lib
 
 
 def _device(*xs):
@@ -240,37 +240,16 @@ MAX_POOL_CHANNELS = 4096
 _INFLUENCE = {"linear": 0, "constant": 1}
 
 
-def _f32(t, name, ncol=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) "
-                         "library and this module has no CPU path")
-    if not t.dtype.is_floating_point:
-        raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
-    if t.dim() != 2 or (ncol is not None and t.shape[1] != ncol):
-        raise ValueError(f"{name} must be (N, {'C' if ncol is None else ncol}), got {tuple(t.shape)}")
-    return t.detach().to(torch.float32).contiguous()
+def _f32(t, name, ncol=None, dev=None):
+    return _front.tensor(t, name, "(N, C)" if ncol is None else "(N, {1})", (None, ncol), dev, "floating",
+                         torch.Tensor.contiguous)
 
 
-def _indices(t, name, rows):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor")
-    if t.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{name} must be torch.int32 or torch.int64, got {t.dtype}")
-    if t.dim() != 2 or t.shape[0] != rows:
-        raise ValueError(f"{name} must be ({rows}, k), got {tuple(t.shape)}")
+def _indices(t, name, rows, dev):
+    t = _front.tensor(t, name, "({0}, k)", (rows, None), dev, "index")
     if not 1 <= t.shape[1] <= MAX_NEIGHBORS:
         raise ValueError(f"{name} has k={t.shape[1]} columns, outside 1..{MAX_NEIGHBORS}")
     return t.contiguous()
-
-
-def _forward_only(what, *tensors):
-    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
-        raise RuntimeError(f"{what} is forward-only (inference): call it under torch.no_grad() or pass "
-                           "detached tensors; it would otherwise silently cut the graph")
 
 
 def kpconv_forward(q_pts, s_pts, s_feats, neigh_inds, kernel_points, weights, KP_extent,
@@ -282,13 +261,13 @@ def kpconv_forward(q_pts, s_pts, s_feats, neigh_inds, kernel_points, weights, KP
     n K C_in is allocated: the output and m bytes of row flags."""
     if KP_influence not in _INFLUENCE:
         raise ValueError(f"KP_influence={KP_influence!r}: 'linear' or 'constant'")
-    _forward_only("kpconv_forward", q_pts, s_pts, s_feats, kernel_points, weights)
+    _front.forward_only("kpconv_forward", q_pts, s_pts, s_feats, kernel_points, weights)
     q = _f32(q_pts, "q_pts", 3)
-    s = _f32(s_pts, "s_pts", 3)
-    f = _f32(s_feats, "s_feats")
-    kp = _f32(kernel_points, "kernel_points", 3)
-    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dim() != 3:
-        raise ValueError("weights must be a CUDA tensor of shape (K, C_in, C_out)")
+    dev = q.device
+    s, f = _f32(s_pts, "s_pts", 3, dev), _f32(s_feats, "s_feats", None, dev)
+    kp = _f32(kernel_points, "kernel_points", 3, dev)
+    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dim() != 3 or weights.device != dev:
+        raise ValueError(f"weights must be a CUDA tensor of shape (K, C_in, C_out) on {dev}")
     w = weights.detach().to(torch.float32).contiguous()
     n, m = q.shape[0], s.shape[0]
     K, c_in, c_out = w.shape
@@ -301,13 +280,10 @@ def kpconv_forward(q_pts, s_pts, s_feats, neigh_inds, kernel_points, weights, KP
                          f"in 1..{MAX_KERNEL_POINTS}")
     if not (1 <= c_in <= MAX_CHANNELS and 1 <= c_out <= MAX_CHANNELS):
         raise ValueError(f"C_in={c_in}, C_out={c_out} must lie in 1..{MAX_CHANNELS}")
-    idx = _indices(neigh_inds, "neigh_inds", n)
-    if any(t.device != q.device for t in (s, f, kp, w, idx)):
-        raise ValueError("all inputs must live on one device")
+    idx = _indices(neigh_inds, "neigh_inds", n, dev)
     ext = float(KP_extent)
     if KP_influence == "linear" and not ext > 0:
         raise ValueError(f"KP_extent={KP_extent} must be > 0")
-    dev = q.device
     out = torch.empty((n, c_out), dtype=torch.float32, device=dev)
     if n == 0:
         return out
@@ -323,16 +299,14 @@ def neighbor_max(feats, inds):
     """MaxPoolBlock.forward (blocks.py:182-188): out[i] = max over the columns of
     feats[inds[i]], a pad (index outside [0, m)) reading 0.  feats (m,C) f32,
     inds (n,k) int32/int64 -> (n,C) f32, exact."""
-    _forward_only("neighbor_max", feats)
+    _front.forward_only("neighbor_max", feats)
     f = _f32(feats, "feats")
     m, c = f.shape
     if m < 1 or not 1 <= c <= MAX_POOL_CHANNELS:
         raise ValueError(f"feats {tuple(f.shape)}: needs m >= 1 and C in 1..{MAX_POOL_CHANNELS}")
     if not isinstance(inds, torch.Tensor) or inds.dim() != 2:
         raise ValueError("inds must be a (n, k) index tensor")
-    idx = _indices(inds, "inds", inds.shape[0])
-    if idx.device != f.device:
-        raise ValueError("all inputs must live on one device")
+    idx = _indices(inds, "inds", inds.shape[0], f.device)
     n = idx.shape[0]
     out = torch.empty((n, c), dtype=torch.float32, device=f.device)
     if n == 0:
@@ -412,19 +386,8 @@ def fuse(model):
     `KP_extent` and aggregation_mode 'sum' becomes a KPConv sharing the same
     parameters, every MaxPoolBlock (by class name, with `layer_ind`) a MaxPool.
     Returns (convolutions swapped, pools swapped)."""
-    n_conv = n_pool = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if _conv_shaped(child):
-                new = KPConv(child.weights.shape[1], child.weights.shape[2], getattr(child, "radius", 0.0),
-                             child.kernel_points, child.KP_extent, getattr(child, "KP_influence", "linear"),
-                             "sum", weights=child.weights)
-                n_conv += 1
-            elif type(child).__name__ == "MaxPoolBlock" and hasattr(child, "layer_ind"):
-                new = MaxPool(child.layer_ind)
-                n_pool += 1
-            else:
-                continue
-            new.train(child.training)
-            setattr(parent, name, new)
-    return n_conv, n_pool
+    kinds = ((_conv_shaped, lambda c: KPConv(c.weights.shape[1], c.weights.shape[2], getattr(c, "radius", 0.0),
+                                             c.kernel_points, c.KP_extent, getattr(c, "KP_influence", "linear"), "sum",
+                                             weights=c.weights)),
+             (("MaxPoolBlock", ("layer_ind",)), lambda c: MaxPool(c.layer_ind)))
+    return _front.swap_children(model, kinds, errors=())

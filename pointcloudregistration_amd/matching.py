@@ -29,7 +29,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _front, _lib
 
 __all__ = ["similarity_topk", "tfmr_match", "tfmr_correspondences"]
 
@@ -37,16 +37,8 @@ MAX_TOPK = 8
 
 
 def _f32(name, t, last=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) "
-                         "library and this module has no CPU path")
-    if t.dim() != 3 or (last is not None and t.shape[2] != last):
-        raise ValueError(f"{name} must be (B, N, {'C' if last is None else last}), got {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
-    return t
+    _front.tensor(t, name, "(B, N, C)" if last is None else "(B, N, {2})", (None, None, last))
+    return t   # not detached: tfmr_match differentiates through the gathered rows
 
 
 def _features(fx, fy, k):
@@ -65,11 +57,9 @@ def _features(fx, fy, k):
 
 
 def _scratch(B, N1, M1, C, k, device):
-    n = _lib.load().pcr_tfmr_scratch_bytes(B, N1, M1, C, k)
-    if n < 0:
-        raise _lib.PcrError("pcr_tfmr_scratch_bytes: " + _lib.load().pcr_last_error().decode())
-    # torch's caching allocator hands out 512-byte aligned blocks; the library checks 256
-    return torch.empty(max(int(n), 1), dtype=torch.uint8, device=device)
+    # never empty: torch's caching allocator hands out 512-byte aligned blocks; the library checks 256
+    return _front.scratch(_lib.load().pcr_tfmr_scratch_bytes(B, N1, M1, C, k), device, at_least=1,
+                          who="pcr_tfmr_scratch_bytes: ")
 
 
 def _topk(fx, fy, B, N1, M1, C, k):
@@ -91,9 +81,8 @@ def similarity_topk(fx, fy, k):
     an input that requires grad while grad mode is on raises instead of silently
     cutting the graph (``tfmr_match`` has the differentiable form)."""
     fx, fy, B, N1, M1, C, k = _features(fx, fy, k)
-    if torch.is_grad_enabled() and (fx.requires_grad or fy.requires_grad):
-        raise RuntimeError("similarity_topk is forward-only: call it under torch.no_grad() or pass "
-                           "detached tensors; tfmr_match differentiates through the top-k values")
+    _front.forward_only("similarity_topk", fx, fy, message="similarity_topk is forward-only: call it under "
+                        "torch.no_grad() or pass detached tensors; tfmr_match differentiates through the top-k values")
     val, idx, _ = _topk(fx, fy, B, N1, M1, C, k)
     return val, idx.long()
 

@@ -31,9 +31,7 @@ import ctypes
 
 import torch
 
-from . import _lib, attention
-from .attention import _scratch
-from .kpconv import _forward_only
+from . import _front, _lib, attention
 
 __all__ = ["unary_forward", "norm_act", "Unary", "NearestUpsample", "Simple", "ResnetBottleneck", "fuse", "forward",
            "MAX_ROWS", "MAX_IN", "MAX_OUT"]
@@ -46,33 +44,11 @@ _STAGES = ("y", "stats")
 
 def _rows(t, name, dev=None):
     """A (rows, c) f32 CUDA tensor with unit stride along c, on its own storage where it has one."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) "
-                         "library and this module has no CPU path")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
-    if t.dim() != 2:
-        raise ValueError(f"{name} must be (rows, channels), got {tuple(t.shape)}")
-    if dev is not None and t.device != dev:
-        raise ValueError(f"{name} on {t.device}, expected {dev}: all inputs must live on one device")
-    t = t.detach()
-    if t.shape[1] and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
-
-
-def _vector(t, name, c, dev):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (c,):
-        raise ValueError(f"{name} must be a ({c},) torch.float32 tensor on {dev}")
-    return t.detach().contiguous()
+    return _front.tensor(t, name, "(rows, channels)", 2, dev, "f32", _front.rows)
 
 
 def _call(x0, weight, gather, x1, bias, norm, eps, slope, act, residual, want, who):
-    _forward_only(who, x0, weight, x1, bias, residual)
+    _front.forward_only(who, x0, weight, x1, bias, residual)
     x0 = _rows(x0, "x0")
     dev = x0.device
     m0, c0 = x0.shape
@@ -123,15 +99,12 @@ def _call(x0, weight, gather, x1, bias, norm, eps, slope, act, residual, want, w
     if not abs(slope) <= 1:
         raise ValueError(f"slope={slope} outside -1..1")
     if bias is not None:
-        bias = _vector(bias, "bias", cout, dev)
+        bias = _front.param(bias, "bias", (cout,), dev)
     if residual is not None:
         residual = _rows(residual, "residual", dev).contiguous()
         if tuple(residual.shape) != (n, cout):
             raise ValueError(f"residual {tuple(residual.shape)} must be ({n}, {cout})")
-    want = tuple(want)
-    for name in want:
-        if name not in _STAGES:
-            raise ValueError(f"want: unknown output {name!r} (one of {', '.join(_STAGES)})")
+    want = _front.wanted(want, _STAGES)
     if "stats" in want and not norm:
         raise ValueError("want: stats without norm")
     out = torch.empty((n, cout), dtype=torch.float32, device=dev)
@@ -156,7 +129,7 @@ def _call(x0, weight, gather, x1, bias, norm, eps, slope, act, residual, want, w
         a.y = outs["y"].data_ptr() if "y" in outs else None
         a.stats = outs["stats"].data_ptr() if "stats" in outs else None
         with torch.cuda.device(dev):
-            ws = _scratch(lib.pcr_unary_scratch_bytes(n, cout), dev)
+            ws = _front.scratch(lib.pcr_unary_scratch_bytes(n, cout), dev)
             _lib.call("pcr_unary_forward", ctypes.byref(a), _lib.ptr(ws), _lib.stream_handle(dev))
     if want:
         return (out,) + tuple(outs[k] for k in want)
@@ -335,10 +308,6 @@ class ResnetBottleneck(torch.nn.Module):
         return _run_unary(self.unary2, q_feats, residual=shortcut, act=True, slope=_slope(self))
 
 
-def _has(mod, *names):
-    return all(hasattr(mod, n) for n in names)
-
-
 def fuse(model, refused=None):
     """Swap a loaded network's blocks for the fused ones, in place: every child of class name
     `UnaryBlock` with mlp (a Linear without bias), bn and relu, every `NearestUpsampleBlock` with
@@ -350,29 +319,12 @@ def fuse(model, refused=None):
     (a list) when one is given.  Returns (UnaryBlock, NearestUpsampleBlock, SimpleBlock,
     ResnetBottleneckBlock) blocks swapped; a second call finds nothing and returns zeros."""
     conv = ("KPConv", "bn", "leaky_relu", "block_name", "layer_ind")
-    kinds = (("UnaryBlock", lambda m: Unary(like=m), ("mlp", "bn", "relu")),
-             ("NearestUpsampleBlock", lambda m: NearestUpsample(m.layer_ind), ("layer_ind",)),
-             ("SimpleBlock", Simple, conv),
-             ("ResnetBottleneckBlock", ResnetBottleneck, conv + ("unary1", "unary2", "unary_shortcut", "max_pool")))
-    counts = [0, 0, 0, 0]
-    for wave in ((0, 1), (2, 3)):   # the leaves first: a swapped block then holds its swapped unaries
-        for pname, parent in list(model.named_modules()):
-            for name, child in list(parent.named_children()):
-                for i in wave:
-                    cls, make, attrs = kinds[i]
-                    if type(child).__name__ != cls or not _has(child, *attrs):
-                        continue
-                    try:
-                        new = make(child)
-                    except ValueError as e:
-                        if refused is not None:
-                            refused.append((f"{pname}.{name}" if pname else name, str(e)))
-                        break
-                    new.train(child.training)
-                    setattr(parent, name, new)
-                    counts[i] += 1
-                    break
-    return tuple(counts)
+    kinds = ((("UnaryBlock", ("mlp", "bn", "relu")), lambda m: Unary(like=m)),
+             (("NearestUpsampleBlock", ("layer_ind",)), lambda m: NearestUpsample(m.layer_ind)),
+             (("SimpleBlock", conv), Simple),
+             (("ResnetBottleneckBlock", conv + ("unary1", "unary2", "unary_shortcut", "max_pool")), ResnetBottleneck))
+    # the leaves first: a swapped block then holds its swapped unaries
+    return _front.swap_children(model, kinds, refused=refused, waves=((0, 1), (2, 3)))
 
 
 # ---- the network's forward ---------------------------------------------------------------

@@ -29,8 +29,7 @@ import ctypes
 
 import torch
 
-from . import _lib
-from .attention import _forward_only, _scratch
+from . import _front, _lib
 
 __all__ = ["fold", "prepare", "describe", "PreparedPointNet", "FusedPointNetFeature", "fuse", "MAX_DIM",
            "MAX_POINTS", "MAX_PATCHES"]
@@ -40,6 +39,7 @@ MAX_POINTS = 4096
 MAX_PATCHES = 1 << 20
 _WIDTHS = {"conv1": (128, 3), "conv2": (256, 128), "fc1": (128, 256)}
 _LAYERS = ("conv1", "conv2", "fc1", "fc2")
+_PATCH_SIZES = (None, 3, None)
 
 
 def fold(linear, bn=None):
@@ -177,23 +177,12 @@ def _patches(patches, prepared=None):
     pcr_pointnet_forward: always the caller's own storage (a detached alias), whatever the
     strides -- a contiguous tensor, the transposed view of a (B, P, 3) one and a batch slice all
     go in without a copy."""
-    x = patches
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("patches must be a torch.Tensor")
-    if x.dtype != torch.float32:
-        raise ValueError(f"patches must be torch.float32, got {x.dtype}")
-    if x.dim() != 3 or x.shape[1] != 3:
-        raise ValueError(f"patches must be (B, 3, P), got {tuple(x.shape)}")
-    if not x.is_cuda:
-        raise ValueError("patches must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) library and this "
-                         "module has no CPU path")
-    if prepared is not None and x.device != prepared.device:
-        raise ValueError(f"patches on {x.device}, weights on {prepared.device}")
+    x = _front.tensor(patches, "patches", "(B, 3, P)", _PATCH_SIZES, prepared.device if prepared is not None else None)
     if not 1 <= x.shape[2] <= MAX_POINTS:
         raise ValueError(f"P={x.shape[2]} outside 1..{MAX_POINTS}")
     if x.shape[0] > MAX_PATCHES:
         raise ValueError(f"B={x.shape[0]} above {MAX_PATCHES}")
-    return x.detach()
+    return x
 
 
 def describe(prepared, patches, want=()):
@@ -203,12 +192,9 @@ def describe(prepared, patches, want=()):
     to the result in the order given."""
     if not isinstance(prepared, PreparedPointNet):
         raise TypeError("prepared must be a PreparedPointNet (pointnet.prepare(net))")
-    _forward_only("pointnet.describe", patches)
+    _front.forward_only("pointnet.describe", patches)
     x = _patches(patches, prepared)
-    want = tuple(want)
-    for name in want:
-        if name not in ("hid", "trans", "xtrans"):
-            raise ValueError(f"want: unknown output {name!r}")
+    want = _front.wanted(want, ("hid", "trans", "xtrans"))
     if "trans" in want and not prepared.tnet:
         raise ValueError("trans requested from a network without a T-net")
     b, _, p = x.shape
@@ -222,7 +208,7 @@ def describe(prepared, patches, want=()):
         lib = _lib.load()
         w = prepared._struct()
         with torch.cuda.device(dev):
-            ws = _scratch(lib.pcr_pointnet_scratch_bytes(b, dim, int(prepared.tnet)), dev)
+            ws = _front.scratch(lib.pcr_pointnet_scratch_bytes(b, dim, int(prepared.tnet)), dev)
             _lib.call("pcr_pointnet_forward", _lib.ptr(x), x.stride(0), x.stride(1), x.stride(2), b, p,
                       ctypes.byref(w), dim, int(prepared.tnet), int(prepared.l2norm), _lib.ptr(f), _lib.ptr(mx),
                       _lib.ptr(amx), _lib.ptr(outs.get("hid")), _lib.ptr(outs.get("trans")),

@@ -31,9 +31,7 @@ import ctypes
 
 import torch
 
-from . import _lib, attention, grouping, groupmlp, matching, procrustes
-from .attention import _scratch
-from .kpconv import _forward_only
+from . import _front, _lib, attention, grouping, groupmlp, matching, procrustes
 
 __all__ = ["pointwise_forward", "PointNet", "MLPs", "CG", "OverlapAttention", "fuse", "forward", "MAX_POINTS",
            "MAX_IN", "MAX_OUT", "MAX_SOURCES"]
@@ -48,30 +46,9 @@ _STAGES = ("out", "max", "y", "stats")
 
 def _cloud(t, name, dev=None, b=None, n=None):
     """A (B, C, N) f32 CUDA tensor with unit stride over points (anything else is copied once)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA (ROCm/HIP) tensor: libpcr is a GPU (gfx950) "
-                         "library and this module has no CPU path")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
-    if t.dim() != 3:
-        raise ValueError(f"{name} must be (B, C, N), got {tuple(t.shape)}")
-    if dev is not None and t.device != dev:
-        raise ValueError(f"{name} on {t.device}, expected {dev}: all inputs must live on one device")
-    if b is not None and (t.shape[0] != b or t.shape[2] != n):
-        raise ValueError(f"{name} {tuple(t.shape)} must be (B={b}, C, N={n})")
-    t = t.detach()
-    return t if t.shape[2] <= 1 or t.stride(2) == 1 else t.contiguous()
-
-
-def _param(t, name, shape, dev):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must be a {tuple(shape)} torch.float32 tensor on {dev}, got "
-                         f"{tuple(t.shape)} {t.dtype} on {t.device}")
-    return t.detach().contiguous()
+    if b is None:
+        return _front.tensor(t, name, "(B, C, N)", 3, dev, "f32", _front.unit_last)
+    return _front.tensor(t, name, "(B={0}, C, N={2})", (b, None, n), dev, "f32", _front.unit_last)
 
 
 def pointwise_forward(sources, weight, *, sub=None, bias=None, cloud_bias=None, groups=0, gamma=None, beta=None,
@@ -96,7 +73,7 @@ def pointwise_forward(sources, weight, *, sub=None, bias=None, cloud_bias=None, 
     subs = (None,) * len(sources) if sub is None else ((sub,) if isinstance(sub, torch.Tensor) else tuple(sub))
     if len(subs) != len(sources):
         raise ValueError(f"sub has {len(subs)} entries for {len(sources)} sources")
-    _forward_only("ropnet.pointwise_forward", *sources, *subs, weight, bias, cloud_bias, gamma, beta, residual)
+    _front.forward_only("ropnet.pointwise_forward", *sources, *subs, weight, bias, cloud_bias, gamma, beta, residual)
     srcs = [_cloud(sources[0], "sources[0]")]
     dev = srcs[0].device
     b, _, n = srcs[0].shape
@@ -140,19 +117,15 @@ def pointwise_forward(sources, weight, *, sub=None, bias=None, cloud_bias=None, 
         raise ValueError(f"eps={eps} must be >= 0")
     if not abs(slope) <= 1:
         raise ValueError(f"slope={slope} outside -1..1")
-    bias = None if bias is None else _param(bias, "bias", (cout,), dev)
-    cloud_bias = None if cloud_bias is None else _param(cloud_bias, "cloud_bias", (b, cout), dev)
-    gamma = None if gamma is None else _param(gamma, "gamma", (cout,), dev)
-    beta = None if beta is None else _param(beta, "beta", (cout,), dev)
+    bias = None if bias is None else _front.param(bias, "bias", (cout,), dev)
+    cloud_bias = None if cloud_bias is None else _front.param(cloud_bias, "cloud_bias", (b, cout), dev)
+    gamma = None if gamma is None else _front.param(gamma, "gamma", (cout,), dev)
+    beta = None if beta is None else _front.param(beta, "beta", (cout,), dev)
     if residual is not None:
         residual = _cloud(residual, "residual", dev, b, n)
         if residual.shape[1] != cout:
             raise ValueError(f"residual {tuple(residual.shape)} must be ({b}, {cout}, {n})")
-    single = isinstance(want, str)
-    want = (want,) if single else tuple(want)
-    for name in want:
-        if name not in _STAGES:
-            raise ValueError(f"want: unknown output {name!r} (one of {', '.join(_STAGES)})")
+    want, single = _front.wanted(want, _STAGES, single=True)
     if not want:
         raise ValueError("want: nothing asked for")
     if "stats" in want and not groups:
@@ -192,7 +165,7 @@ def pointwise_forward(sources, weight, *, sub=None, bias=None, cloud_bias=None, 
         a.y = outs["y"].data_ptr() if "y" in outs else None
         a.stats = outs["stats"].data_ptr() if "stats" in outs else None
         with torch.cuda.device(dev):
-            ws = _scratch(lib.pcr_pointwise_scratch_bytes(b, n, cout), dev)
+            ws = _front.scratch(lib.pcr_pointwise_scratch_bytes(b, n, cout), dev)
             _lib.call("pcr_pointwise_forward", ctypes.byref(a), _lib.ptr(ws), _lib.stream_handle(dev))
     got = tuple(outs[k] for k in want)
     return got[0] if single or len(got) == 1 else got
@@ -383,7 +356,7 @@ class CG(torch.nn.Module):
     def forward(self, src, tgt):
         """src (B, N, 3), tgt (B, M, 3) -> T0 (B, 3, 4), x_ol (B, 2, N), y_ol (B, 2, M)."""
         _eval_only(self, "ropnet.CG")
-        _forward_only("ropnet.CG", src, tgt, *self.parameters())
+        _front.forward_only("ropnet.CG", src, tgt, *self.parameters())
         f_x, g_x = self.encoder(src.permute(0, 2, 1).contiguous())
         f_y, g_y = self.encoder(tgt.permute(0, 2, 1).contiguous())
         out = self.decoder_qt((g_x, g_y))
@@ -437,16 +410,12 @@ class OverlapAttention(torch.nn.Module):
     def forward(self, x, ol=None):
         """x (B, C, N), ol (B, N) or None -> (B, 5 C, N)."""
         _eval_only(self, "ropnet.OverlapAttention")
-        _forward_only("ropnet.OverlapAttention", x, ol, *self.parameters())
+        _front.forward_only("ropnet.OverlapAttention", x, ol, *self.parameters())
         xs = []
         for name in _BLOCKS:
             x = self._block(getattr(self, name), x, ol)
             xs.append(x)
         return _run_layer(_layers(self.conv_fuse, "OverlapAttention.conv_fuse")[0], xs)
-
-
-def _has(mod, *names):
-    return all(hasattr(mod, n) for n in names)
 
 
 def fuse(model, refused=None):
@@ -458,27 +427,10 @@ def fuse(model, refused=None):
     module with a kernel size other than 1, an unknown norm or another structure is left in place; its
     name and the reason are appended to `refused` (a list) when one is given.  Returns (CGModule,
     OverlapAttention) swapped; a second call finds nothing and returns zeros."""
-    kinds = (("CGModule", CG, ("encoder", "decoder_ol", "decoder_qt")),
-             ("OverlapAttention", OverlapAttention, _BLOCKS + ("conv_fuse",)))
-    counts = [0, 0]
-    for pname, parent in list(model.named_modules()):
-        for name, child in list(parent.named_children()):
-            if isinstance(child, (CG, OverlapAttention)):
-                continue
-            for i, (cls, new_type, attrs) in enumerate(kinds):
-                if type(child).__name__ != cls or not _has(child, *attrs):
-                    continue
-                try:
-                    new = new_type(child)
-                except (ValueError, AttributeError) as e:
-                    if refused is not None:
-                        refused.append((f"{pname}.{name}" if pname else name, str(e)))
-                    break
-                new.train(child.training)
-                setattr(parent, name, new)
-                counts[i] += 1
-                break
-    return tuple(counts)
+    kinds = ((("CGModule", ("encoder", "decoder_ol", "decoder_qt")), CG),
+             (("OverlapAttention", _BLOCKS + ("conv_fuse",)), OverlapAttention))
+    return _front.swap_children(model, kinds, refused=refused, errors=(ValueError, AttributeError),
+                                skip=(CG, OverlapAttention))
 
 
 # ---- the network's forward ---------------------------------------------------------------
@@ -517,7 +469,7 @@ def forward(model, src, tgt, num_iter=1):
     if model.training:
         raise RuntimeError("ropnet.forward: the model is in training mode; this module is forward-only, "
                            "call model.eval()")
-    _forward_only("ropnet.forward", src, tgt, *model.parameters())
+    _front.forward_only("ropnet.forward", src, tgt, *model.parameters())
     if num_iter < 1:
         raise ValueError(f"num_iter={num_iter}: the reference's result needs at least one iteration")
     tfmr = model.tfmr
