@@ -254,6 +254,38 @@ int pcr_icp_batch(const float *src_xyz, const float *tgt_xyz, int32_t P, int32_t
                   const pcr_icp_params *params, double *T, double *fitness_rmse, int32_t *stats,
                   int32_t *corr_tgt, pcr_stream_t stream);
 
+/* Robust kernel of point-to-plane ICP (Open3D RobustKernel): the weight of a
+ * residual r, a = |r|.  k > 0 is the kernel's scale (unused by L2). */
+enum {
+    PCR_KERNEL_L2 = 0,     /* 1 */
+    PCR_KERNEL_HUBER = 1,  /* a <= k ? 1 : k / a */
+    PCR_KERNEL_CAUCHY = 2, /* 1 / (1 + (r/k)^2) */
+    PCR_KERNEL_GM = 3,     /* k / (k + r^2)^2 */
+    PCR_KERNEL_TUKEY = 4   /* a <= k ? (1 - (r/k)^2)^2 : 0 */
+};
+
+typedef struct pcr_icp_plane_params {
+    int32_t kernel;   /* PCR_KERNEL_* */
+    int32_t reserved;
+    double k;
+} pcr_icp_plane_params;
+
+/* ---------------------------------------------------------------------------
+ * Point-to-plane ICP with a robust kernel (Open3D registration_icp with
+ * TransformationEstimationPointToPlane(kernel)).  As pcr_icp_batch, with
+ * tgt_normals (P,Mmax,3) f32, the targets' normals, and the loop's Umeyama
+ * step replaced by the weighted point-to-plane Gauss-Newton update (DESIGN.md
+ * "Point-to-plane ICP").  The loop, the correspondence search, the stop rule
+ * and the outputs are pcr_icp_batch's.  P == 0 returns PCR_OK; a null pointer
+ * (corr_tgt, n_src and n_tgt may be null), a negative size, an unknown kernel
+ * or k <= 0 for a kernel that uses it return PCR_ERR_ARG.
+ * ------------------------------------------------------------------------- */
+int pcr_icp_plane_batch(const float *src_xyz, const float *tgt_xyz, const float *tgt_normals,
+                        int32_t P, int32_t Nmax, int32_t Mmax, const int32_t *n_src,
+                        const int32_t *n_tgt, const double *init, const pcr_icp_params *params,
+                        const pcr_icp_plane_params *plane, double *T, double *fitness_rmse,
+                        int32_t *stats, int32_t *corr_tgt, pcr_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * The C4 pipeline step (DataPreparation/RANSAC.py:109-122 per pair, with the
  * QualityCheck.py:25-31 Chamfer) for P resident pairs, no host round trip:

@@ -48,6 +48,11 @@ class IcpParams(ctypes.Structure):
                 ("relative_rmse", _f64), ("max_iteration", _i32), ("reserved", _i32)]
 
 
+class IcpPlaneParams(ctypes.Structure):
+    """pcr_icp_plane_params (include/pcr_api.h)."""
+    _fields_ = [("kernel", _i32), ("reserved", _i32), ("k", _f64)]
+
+
 class PointNetLayers(ctypes.Structure):
     """pcr_pointnet_layers (include/pcr_api.h): one branch's folded weights, device pointers."""
     _fields_ = [(n, _p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4")]
@@ -83,6 +88,7 @@ class PointwiseArgs(ctypes.Structure):
 
 _rp = ctypes.POINTER(RansacParams)
 _ip = ctypes.POINTER(IcpParams)
+_ipp = ctypes.POINTER(IcpPlaneParams)
 
 # name -> argtypes (restype is always c_int); keep in sync with include/pcr_api.h
 SIGNATURES = {
@@ -100,6 +106,7 @@ SIGNATURES = {
     "pcr_register_feature_ransac": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _rp,
                                     _p, _p, _p, _p, _p, _p],
     "pcr_icp_batch": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _ip, _p, _p, _p, _p, _p],
+    "pcr_icp_plane_batch": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _ip, _ipp, _p, _p, _p, _p, _p],
     "pcr_radius_nn": [_p, _i32, _i32, _p, _p, _i32, _p, _f64, _p, _p, _p],
     "pcr_procrustes_batch": [_p, _p, _p, _i32, _i32, _i32, _f64, _p, _p],
     "pcr_procrustes_batch_f64": [_p, _p, _p, _i32, _i32, _i32, _f64, _p, _p],

@@ -26,12 +26,12 @@
 //    workgroup on the same totals.
 #include "pcr_internal.h"
 #include "coop.h"
+#include "exact_sums.h"
 #include "geom.h"
 #include "grid.h"
 #include "wave.h"
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
 #include <vector>
 
 namespace pcr {
@@ -40,13 +40,6 @@ namespace {
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
 constexpr int kQ = 15;  // exact sums: s' (3), t' (3), s'_a t'_b (9)
-
-// one workgroup's partial of a reduction (G > 1): HBM slot per (pair, parity, g)
-struct XPart {
-    double s[kQ];
-    unsigned long long acc;
-    int cnt, pad;
-};
 
 struct IArgs {
     const float *src, *tgt;
@@ -72,27 +65,12 @@ struct IArgs {
     int *ctl;            // [0] pairs still iterating in phase 1, [1] listed pairs
     int *list;           // (P) listed pairs
     double *save;        // (P, kSave) the listed pairs' state
-    XPart *part;         // (P, 2, G) when G > 1
+    XPart<kQ> *part;     // (P, 2, G) when G > 1
     // when G > 1: per pair 4 words at bar + 4 p, the pair barrier (arrivals,
     // generation)
     unsigned *bar;
     unsigned long long *timing;  // debug (PCR_ICP_TIMING): per pair, phase clocks
 };
-
-// The working copy when a pair has G > 1 workgroups: each pair barrier's
-// release fence writes back the XCD L2's dirty lines, and a sweep dirtied ~48 KB
-// of working copy per workgroup (2,048 points x 24 B at 32 pairs, G = 4).
-// Stored write-through (sc1: the line leaves L2 clean) there is nothing of it to
-// write back; visibility is still the barrier's release / acquire.
-__device__ __forceinline__ void put3(double *q, double x, double y, double z, bool wt) {
-    if (wt) {
-        __hip_atomic_store(q, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(q + 1, y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(q + 2, z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        q[0] = x; q[1] = y; q[2] = z;
-    }
-}
 
 // Correspondence reuse.  A point's grid walk also reports the two smallest
 // distances it computed and a lower bound rho on the distance to any target it
@@ -144,100 +122,6 @@ struct IShared {  // LDS header; the grid copy (if any) follows
     int pend[kWaves][128];  // per wave: positions waiting for a grid walk (a stack)
     int nwalk;        // debug (PCR_ICP_PHASES): walks done by this workgroup
 };
-
-// wave-level sums of the kQ exact f64 values (integer multiples of the quantum:
-// the additions are exact, so the tree shape is free), parked in
-// sh.ws[wave][0..kQ).  A reduce-scatter butterfly: at each of the offsets 32,
-// 16, 8, 4 a lane keeps half of its values and adds its partner's copy of that
-// half (8 + 4 + 2 + 1 shuffles instead of 6 per value), then offsets 2, 1 finish
-// the one value left -- lane l ends with value (l >> 2) summed over the wave.
-__device__ __forceinline__ void wave_park(IShared &sh, const double *v) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    double w[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) w[q] = q < kQ ? v[q] : 0.0;
-    auto step = [&](auto hc) {
-        constexpr int h = decltype(hc)::value, o = 4 * h;
-        const bool up = (lane & o) != 0;  // keeps the upper half
-#pragma unroll
-        for (int i = 0; i < h; ++i) {
-            const double keep = up ? w[i + h] : w[i], send = up ? w[i] : w[i + h];
-            w[i] = keep + __shfl_xor(send, o, 64);
-        }
-    };
-    step(std::integral_constant<int, 8>{});
-    step(std::integral_constant<int, 4>{});
-    step(std::integral_constant<int, 2>{});
-    step(std::integral_constant<int, 1>{});
-    double t = w[0];
-    t += __shfl_xor(t, 2, 64);
-    t += __shfl_xor(t, 1, 64);
-    // lane bits 5..2 picked the half at offsets 32..4: lane l holds value
-    // (l >> 5 & 1) * 8 + (l >> 4 & 1) * 4 + (l >> 3 & 1) * 2 + (l >> 2 & 1)
-    const int q = lane >> 2;
-    if ((lane & 3) == 0 && q < kQ) sh.ws[wid][q] = t;
-}
-
-// sum the NV parked values + (cnt, acc) over the pair's workgroups; result in
-// sh.tot / sh.cnt / sh.acc (all threads call; ends with a barrier)
-// mk(ph): debug phase clocks (PCR_ICP_PHASES): 5 = the workgroup's waves
-// joined, 6 = the pair barrier passed
-template <int NV, typename Mark>
-__device__ void pair_reduce(const IArgs &a, IShared &sh, int p, int g, int G, int cnt,
-                            unsigned long long acc, Mark mk) {
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        cnt += __shfl_xor(cnt, o, 64);
-        acc += __shfl_xor(acc, o, 64);
-    }
-    if (lane == 0) {
-        sh.wcnt[wid] = cnt;
-        sh.wacc[wid] = acc;
-    }
-    __syncthreads();
-    mk(5);
-    if (tid < NV + 2) {  // thread q sums quantity q (NV: count, NV+1: error sum)
-        double s = 0.0;
-        unsigned long long A = 0;
-        int C = 0;
-        for (int w = 0; w < kWaves; ++w) {
-            if (tid < NV) s += sh.ws[w][tid];
-            else if (tid == NV) C += sh.wcnt[w];
-            else A += sh.wacc[w];
-        }
-        if (G > 1) {
-            XPart &me = a.part[((size_t)p * 2 + (sh.nred & 1)) * G + g];
-            if (tid < NV) me.s[tid] = s;
-            else if (tid == NV) me.cnt = C;
-            else me.acc = A;
-        } else {
-            if (tid < NV) sh.tot[tid] = s;
-            else if (tid == NV) sh.cnt = C;
-            else sh.acc = A;
-        }
-    }
-    if (G > 1) {
-        pair_barrier(a.bar + 4 * (size_t)p, G);
-        mk(6);
-        if (tid < NV + 2) {
-            const XPart *all = a.part + ((size_t)p * 2 + (sh.nred & 1)) * G;
-            double s = 0.0;
-            unsigned long long A = 0;
-            int C = 0;
-            for (int h = 0; h < G; ++h) {
-                if (tid < NV) s += all[h].s[tid];
-                else if (tid == NV) C += all[h].cnt;
-                else A += all[h].acc;
-            }
-            if (tid < NV) sh.tot[tid] = s;
-            else if (tid == NV) sh.cnt = C;
-            else sh.acc = A;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) sh.nred += 1;  // read only by threads < NV + 2 after the next barrier
-}
 
 template <bool kLds>
 __global__ __launch_bounds__(kThreads) void icp_kernel(IArgs a) {
@@ -483,9 +367,9 @@ __global__ __launch_bounds__(kThreads) void icp_kernel(IArgs a) {
             if (lane < np) walk(sh.pend[wid][lane]);  // the rest of the stack
         }
         mark(0);
-        wave_park(sh, v);
+        wave_park<kQ>(sh, v);
         mark(4);
-        pair_reduce<kQ>(a, sh, p, g, G, cnt, acc, mark);
+        pair_reduce<kQ>(a.part, a.bar, sh, p, g, G, cnt, acc, mark);
         // every workgroup has left this sweep (pair_reduce's barrier): re-arm its
         // counter for the sweep after next (the next sweep uses the other one,
         // re-armed one reduction ago)
@@ -692,9 +576,9 @@ int icp_impl(const float *src, const float *tgt, int P, int Nmax, int Mmax, cons
     bool *icp_dirty = nullptr;
     if (a.G > 1 || two_phase) {
         const int gp = two_phase ? a.gmax2 : a.G;  // partial slots per pair
-        char *cw = (char *)workspace(kWsIcpPartials_RadiusNnGrid, sizeof(XPart) * 2 * (size_t)gp * (size_t)P + 64);
+        char *cw = (char *)workspace(kWsIcpPartials_RadiusNnGrid, sizeof(XPart<kQ>) * 2 * (size_t)gp * (size_t)P + 64);
         PCR_REQUIRE(cw, PCR_ERR_NOMEM, "icp: %s", pcr_last_error());
-        a.part = (XPart *)cw;
+        a.part = (XPart<kQ> *)cw;
         // barriers in a slot of their own, zeroed when allocated: every launch
         // leaves the arrivals zero (a barrier resets them) and the barrier
         // works from any generation, so no memset per call; the

@@ -12,7 +12,10 @@ namespace pcr {
 // One name per slot of workspace() (runtime.cpp).  The values are the table
 // index and do not change; a new slot goes before kWsCount.  A name with an
 // underscore is one slot with several owners: its comment says why they are
-// never live together.
+// never live together.  icp_plane.hip (pcr_icp_plane_batch) uses icp.hip's
+// slots for the same contents -- grid, order, permuted sources, working copy,
+// partial sums (27 per record instead of 15), barriers: another ABI call, and
+// the barrier words' protocol is the same.
 enum WsSlot : int {
     kWsNone = -1,                 // fpfh.hip run_search: "no list slot" (the caller's own buffers)
     kWsNndPartials = 0,           // nnd.hip: split sweep's partial (dist, idx); pcr_nnd_forward

@@ -243,7 +243,14 @@ def register_feature_ransac_batch(src, tgt, src_feat, tgt_feat, params: RansacPa
     return BatchResult(T, fr[:, 0], fr[:, 1], st, ct, mk)
 
 
-def icp_batch(src, tgt, init, params: IcpParams, n_src=None, n_tgt=None, want_corr=True):
+def icp_batch(src, tgt, init, params: IcpParams, n_src=None, n_tgt=None, want_corr=True,
+              estimation=None, tgt_normals=None):
+    """Batched ICP.  estimation None or TransformationEstimationPointToPoint: point-to-point
+    (pcr_icp_batch).  TransformationEstimationPointToPlane(kernel): point-to-plane with the
+    kernel's weights (pcr_icp_plane_batch); tgt_normals (P, M, 3) are the targets' normals."""
+    plane = _plane_params(estimation)   # raises before anything touches the GPU
+    if plane is not None and tgt_normals is None:
+        raise ValueError("point-to-plane ICP needs tgt_normals (the target's normals)")
     S = _batch3(src, "src")
     G = _batch3(tgt, "tgt", S.device)
     P, N, M = S.shape[0], S.shape[1], G.shape[1]
@@ -254,10 +261,19 @@ def icp_batch(src, tgt, init, params: IcpParams, n_src=None, n_tgt=None, want_co
     ct = torch.empty(P, N, dtype=torch.int32, device=S.device) if want_corr else None
     cp = params.to_c()
     ns, nt = _counts(n_src, P, S.device), _counts(n_tgt, P, S.device)
+    if plane is None:
+        with torch.cuda.device(S.device):
+            _lib.call("pcr_icp_batch", _lib.ptr(S), _lib.ptr(G), P, N, M, _lib.ptr(ns), _lib.ptr(nt),
+                      _lib.ptr(I), ctypes.byref(cp), _lib.ptr(T), _lib.ptr(fr), _lib.ptr(st),
+                      _lib.ptr(ct), _stream(S.device))
+        return BatchResult(T, fr[:, 0], fr[:, 1], st, ct)
+    Nr = _batch3(tgt_normals, "tgt_normals", S.device)
+    if Nr.shape != G.shape:
+        raise ValueError("tgt_normals must have the targets' shape (P, M, 3)")
     with torch.cuda.device(S.device):
-        _lib.call("pcr_icp_batch", _lib.ptr(S), _lib.ptr(G), P, N, M, _lib.ptr(ns), _lib.ptr(nt),
-                  _lib.ptr(I), ctypes.byref(cp), _lib.ptr(T), _lib.ptr(fr), _lib.ptr(st),
-                  _lib.ptr(ct), _stream(S.device))
+        _lib.call("pcr_icp_plane_batch", _lib.ptr(S), _lib.ptr(G), _lib.ptr(Nr), P, N, M, _lib.ptr(ns),
+                  _lib.ptr(nt), _lib.ptr(I), ctypes.byref(cp), ctypes.byref(plane), _lib.ptr(T),
+                  _lib.ptr(fr), _lib.ptr(st), _lib.ptr(ct), _stream(S.device))
     return BatchResult(T, fr[:, 0], fr[:, 1], st, ct)
 
 
@@ -356,6 +372,75 @@ class TransformationEstimationPointToPoint:
         if with_scaling:
             raise NotImplementedError("with_scaling=True (Sim3 Umeyama) is not on the hot path")
         self.with_scaling = False
+
+
+class RobustKernel:
+    """o3d.pipelines.registration.RobustKernel: the weight of a point-to-plane residual r
+    (include/pcr_api.h PCR_KERNEL_*).  k > 0 is the kernel's scale."""
+    kernel_id = 0
+    uses_k = True
+
+    def __init__(self, k=1.0):
+        self.k = float(k)
+
+
+class L2Loss(RobustKernel):
+    """weight 1."""
+    uses_k = False
+
+    def __init__(self):
+        super().__init__(1.0)
+
+
+class L1Loss(RobustKernel):
+    """weight 1 / |r|: refused -- it has no supremum, so the exact sums have no quantum."""
+    kernel_id = -1
+    uses_k = False
+
+    def __init__(self):
+        super().__init__(1.0)
+
+
+class HuberLoss(RobustKernel):
+    """|r| <= k ? 1 : k / |r|."""
+    kernel_id = 1
+
+
+class CauchyLoss(RobustKernel):
+    """1 / (1 + (r / k)^2)."""
+    kernel_id = 2
+
+
+class GMLoss(RobustKernel):
+    """k / (k + r^2)^2."""
+    kernel_id = 3
+
+
+class TukeyLoss(RobustKernel):
+    """|r| <= k ? (1 - (r / k)^2)^2 : 0."""
+    kernel_id = 4
+
+
+class TransformationEstimationPointToPlane:
+    def __init__(self, kernel=None):
+        self.kernel = L2Loss() if kernel is None else kernel
+
+
+def _plane_params(estimation):
+    """pcr_icp_plane_params of an estimation method; None for point-to-point."""
+    if estimation is None or isinstance(estimation, TransformationEstimationPointToPoint):
+        return None
+    if not isinstance(estimation, TransformationEstimationPointToPlane):
+        raise NotImplementedError("only TransformationEstimationPointToPoint and "
+                                  "TransformationEstimationPointToPlane are supported")
+    kern = estimation.kernel
+    if isinstance(kern, L1Loss):
+        raise NotImplementedError("L1Loss is not supported: its weight 1 / |r| is unbounded")
+    if not isinstance(kern, RobustKernel):
+        raise NotImplementedError(f"kernel {type(kern).__name__} is not supported")
+    if kern.uses_k and not kern.k > 0.0:
+        raise ValueError(f"{type(kern).__name__}: k must be > 0 (k={kern.k})")
+    return _lib.IcpPlaneParams(int(kern.kernel_id), 0, float(kern.k))
 
 
 class CorrespondenceCheckerBasedOnEdgeLength:
@@ -468,15 +553,24 @@ def registration_ransac_based_on_correspondence(source, target, corres,
 
 def registration_icp(source, target, max_correspondence_distance, init=None,
                      estimation_method=None, criteria=None):
-    """Drop-in for o3d.pipelines.registration.registration_icp (point-to-point)."""
-    if estimation_method is not None and not isinstance(estimation_method,
-                                                        TransformationEstimationPointToPoint):
-        raise NotImplementedError("only TransformationEstimationPointToPoint is supported")
+    """Drop-in for o3d.pipelines.registration.registration_icp: point-to-point, or
+    point-to-plane (with a robust kernel) on the target's normals."""
+    plane = _plane_params(estimation_method) is not None
+    normals = None
+    if plane:
+        normals = getattr(target, "normals", None)
+        if normals is None or len(normals) == 0:
+            raise ValueError("point-to-plane ICP needs target normals: the target has none "
+                             "(features.estimate_normals computes them)")
+        if not isinstance(normals, torch.Tensor):
+            normals = np.asarray(normals, dtype=np.float64)
+        normals = normals.reshape(1, -1, 3)
     crit = criteria or ICPConvergenceCriteria()
     init = np.eye(4) if init is None else np.asarray(init, dtype=np.float64)
     prm = IcpParams(float(max_correspondence_distance), crit.relative_fitness,
                     crit.relative_rmse, crit.max_iteration)
-    br = icp_batch(_points(source), _points(target), init.reshape(1, 4, 4), prm)
+    br = icp_batch(_points(source), _points(target), init.reshape(1, 4, 4), prm,
+                   estimation=estimation_method if plane else None, tgt_normals=normals)
     return _to_result(br)
 
 
